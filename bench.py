@@ -9,7 +9,8 @@
 A "step" = one pass of the hot path over one batch: 256 L2-normalised query vectors scored against the rank's
 row shard (10M x 768 fp16 per GPU by default = BASELINE.json configs[2]; N GPUs hold N x 10M rows = configs[3]
 at N = 8), fused MFMA scoring + top-10, and for N > 1 the RCCL all-gather of per-shard (score, id) candidates and
-the final merge.  Inputs (index, queries) are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+the final merge.  Inputs (index, queries) are resident in HBM before the timed region.  Rank 0 prints ONE JSON line;
+with ``--dump-outputs DIR`` it also writes the scores and ids the last timed step returned under DIR (``dump_outputs``).
 
 Protocol: W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize pairs
 (``ms_per_step`` / ``value`` come from that wall-clock bracket, max over ranks); every timed step is also bracketed by
@@ -50,7 +51,7 @@ def ensure_library():
     build.build()
 
 
-def spawn_ranks(n: int) -> int:
+def spawn_ranks(n: int, dump_outputs=None) -> int:
     """`python bench.py --gpus N` without a launcher: start `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
     --master-addr 127.0.0.1 --master-port <free> bench.py <the same arguments>` as a child process (never an exec: this
     process stays the parent and has not initialised the GPU -- counting devices does not), pass rank 0's single JSON line
@@ -73,8 +74,10 @@ def spawn_ranks(n: int) -> int:
         port = sk.getsockname()[1]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: RCCL's intra-node transport needs it on this driver
+    # the ranks run in ROOT: a relative --dump-outputs DIR is passed on resolved against this process's directory (the last one counts)
+    extra = ["--dump-outputs", os.path.abspath(dump_outputs)] if dump_outputs else []
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
+           "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:], *extra]
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, text=True, cwd=ROOT)
     for line in proc.stdout:
         (sys.stdout if line.startswith("{") else sys.stderr).write(line)
@@ -259,7 +262,10 @@ def main():
     ap.add_argument("--e2e-steps", type=int, default=30)
     ap.add_argument("--no-sketch", action="store_true", help="no int8 sketch: the exact scan of the index type (profiling runs)")
     ap.add_argument("--no-other", action="store_true", help="skip the other_configs legs (fp8, fp32 + encoder, configs[0] API latency)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # RCCL's intra-node transport needs dmabuf IPC on this driver (hipIpcGetMemHandle fails in the legacy mode): set before torch is
     # imported / anything touches the GPU, for EVERY way this file is started -- bare, self-spawned or under an external launcher
@@ -268,7 +274,7 @@ def main():
     if args.gpus > 1 and not launched:
         # a bare `python bench.py --gpus N`: this process becomes the launcher of its own N ranks (a CHILD torch.distributed.run
         # job, started before anything here has touched the GPU) and relays rank 0's JSON line and the job's exit code
-        sys.exit(spawn_ranks(args.gpus))
+        sys.exit(spawn_ranks(args.gpus, args.dump_outputs))
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -352,6 +358,8 @@ def main():
     kernel_ms, launches = index.get_timing()
     index.set_timing(False)
     step_ms = [e0.elapsed_time(e1) for e0, e1 in ev]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(np, args.dump_outputs, *out)
     multi = None
     if world > 1:
         # max over ranks decides value / ms_per_step; every rank's own bracket is kept beside it
@@ -608,6 +616,26 @@ def main():
     if world > 1:
         dist.barrier()  # rank 0's recall check (CPU oracle, tens of seconds) ends before any rank tears the group down
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(np, path, scores, ids):
+    """What a caller of the timed path received from its last step: ``scores.npy`` [B, k] float32 and ``ids.npy`` [B, k] (float64,
+    exact below 2^53).  The inputs are seeded, so two builds run with the same arguments can be compared file by file.  If the two
+    arrays would exceed DUMP_LIMIT_BYTES, a fixed seeded sample of query rows is written instead, their row numbers in ``query_rows.npy``."""
+    s = scores.float().cpu().numpy()
+    i = ids.cpu().numpy().astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    row_bytes = s.shape[1] * (4 + 8)
+    if s.shape[0] * row_bytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)  # 8: the row number; 4096: three .npy headers
+        rows = np.sort(np.random.default_rng(0).choice(s.shape[0], size=keep, replace=False))
+        s, i = s[rows], i[rows]
+        np.save(os.path.join(path, "query_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "scores.npy"), s)
+    np.save(os.path.join(path, "ids.npy"), i)
 
 
 def step_bytes(info, stats, n, d, esize, b, step_ms):

@@ -1,14 +1,15 @@
 """One rank of the jobs tests/test_gpu_sharded_exec.py starts with
-``python -m torch.distributed.run --nproc-per-node R`` (R = 1, 2 or 8).
+``python -m torch.distributed.run --nproc-per-node R`` (R = 1, 2 or 4).
 
 Runs the REAL sharded path -- DeviceIndex.search (HIP) -> dist.all_gather_into_tensor -> vqa_merge_topk (HIP) -- and
 asserts on every rank that the result equals, bit for bit, the single-shard search of the concatenated corpus on the
 same device and in the same storage type (fp16, fp8 e4m3, fp32): exact ties on both sides of and straddling every shard
 boundary, a row count the world size does not divide, ranks with fewer rows than k, an id vector, string ids, k > 12,
-the R * k = 8192 limit of the merge (8 ranks x 1024 candidates: what a hybrid search at limit >= 103 asks for), the
+1024 candidates per rank into the merge (what a hybrid search at limit >= 103 asks for), the
 per-rank-slice build, the row-producer build and the sharded save -> load round trip (fp16 and fp8).
-``--share`` puts every rank on cuda:0 (gloo, since RCCL refuses two ranks on one device); without it every rank takes its
-own GPU over nccl (= RCCL).  A world of ONE rank over nccl with VQA_ALWAYS_GATHER=1 takes every collective call of the
+``--share`` puts every rank on cuda:0; without it every rank takes its own GPU.  ``--backend nccl`` (= RCCL) with ``--share``:
+RCCL refuses two ranks of one host on one device, so every rank names itself a host of its own (NCCL_HOSTID) and the ranks
+talk over RCCL's network transport, on the interface the caller names (NCCL_SOCKET_IFNAME).  A world of ONE rank over nccl with VQA_ALWAYS_GATHER=1 takes every collective call of the
 path through RCCL on a 1-GPU box.
 """
 import argparse
@@ -39,6 +40,8 @@ def main():
     torch.cuda.set_device(dev_index)
     device = torch.device("cuda", dev_index)
     if args.backend == "nccl":
+        if args.share:
+            os.environ["NCCL_HOSTID"] = f"vqa-rank-{rank}"  # read by RCCL at communicator creation
         dist.init_process_group("nccl", device_id=device)
     else:
         dist.init_process_group("gloo")
@@ -74,7 +77,7 @@ def main():
         checks.append(name)
 
     rng = np.random.default_rng(5)
-    n, d, b, k = 6001, 96, 37, 10  # 6001 = 8 * 750 + 1: ragged over 2 and over 8 ranks
+    n, d, b, k = 6001, 96, 37, 10  # 6001 = 4 * 1500 + 1: ragged over 2 and over 4 ranks
     x = unit(rng, n, d)
     bounds = [shard_bounds(n, world, r) for r in range(world)]
     lo1 = bounds[-1][0]
@@ -131,7 +134,7 @@ def main():
     emb4.index_vectors(None, lambda a, c: x[a:c], total=n, chunk_rows=1000)
     compare("producer", emb4, q, k, single(x, None, q, k, id_base=0))
     # 6. shards shorter than k: 15 rows over the ranks, k = 10 (padding candidates (-inf, -1) take part in the merge);
-    #    with 8 ranks every shard holds one or two rows
+    #    with 4 ranks every shard holds three or four rows
     xs = unit(rng, 15, d)
     emb5 = Embeddings(dtype="fp16", device=dev_index, min_score=None)
     emb5.index_vectors(list(range(1, 16)), xs)  # contiguous ids: id_base path
@@ -170,16 +173,21 @@ def main():
             compare("fp8-save-load", e2, q, k, r_dt)
         e._index.close()
 
-    # 9. the merge at its R * k limit: 1024 candidates per rank (what hybrid search asks for from limit = 103 on) -- at 8
-    #    ranks R * k = 8192 = the documented maximum of vqa_merge_topk; shards of 750 rows pad their lists with (-inf, -1)
+    # 9. 1024 candidates per rank (what hybrid search asks for from limit = 103 on; at 8 ranks R * k = 8192 = the documented
+    #    maximum of vqa_merge_topk); shards shorter than 1024 rows pad their lists with (-inf, -1): the first 3001 rows of
+    #    the corpus over 4 ranks are shards of 750 or 751 rows
     n2 = 20011
     x2 = unit(rng, n2, 64)
     q2 = torch.from_numpy(unit(rng, 5, 64)).to(device)
     e9 = Embeddings(dtype="fp16", device=dev_index, min_score=None)
     e9.index_vectors(None, x2)
     compare("k=1024", e9, q2, 1024, single(x2, None, q2, 1024))
-    compare("k=1024-short-shards", emb, q[:3], 1024, single(x, ids, q[:3], 1024))
     e9._index.close()
+    n9 = 3001
+    e9s = Embeddings(dtype="fp16", device=dev_index, min_score=None)
+    e9s.index_vectors(ids[:n9].tolist(), x[:n9])
+    compare("k=1024-short-shards", e9s, q[:3], 1024, single(x[:n9], ids[:n9], q[:3], 1024))
+    e9s._index.close()
     # ... and through the hybrid (dense + BM25) entry point that produces such a k: index(documents) with a text encoder
     # (every rank encodes only its own shard: the row-producer path), batchsearch(list[str], limit = 103)
     texts = [f"tok{j} grp{j % 13} fam{j % 101}" for j in range(n2)]

@@ -161,16 +161,17 @@ def test_argument_errors(native_lib):
 def test_merge_topk_matches_oracle(native_lib):
     from vietnamese_qa_system_amd.index import merge_topk
     rng = np.random.default_rng(3)
-    r, b, k = 8, 50, 10
-    sc = np.sort(rng.standard_normal((r, b, k)).astype(np.float32), axis=2)[:, :, ::-1].copy()
-    sc[:, :, 5:] = sc[:, :, 4:5]  # ties inside and across shards
-    ids = rng.integers(0, 1 << 40, size=(r, b, k)).astype(np.int64)
-    sc[3, :, 7:] = -np.inf
-    ids[3, :, 7:] = -1  # a short shard
-    es, ei = R.merge_shards(np.where(ids < 0, -np.inf, sc), ids, k)
-    gs, gi = merge_topk(torch.from_numpy(sc).cuda(), torch.from_numpy(ids).cuda(), k)
-    assert np.array_equal(gs.cpu().numpy(), es)
-    assert np.array_equal(gi.cpu().numpy(), ei)
+    # eight ranks; k = 1024 puts R * k at the documented limit of 8192 candidates per query
+    for r, b, k in ((8, 50, 10), (8, 5, 1024)):
+        sc = np.sort(rng.standard_normal((r, b, k)).astype(np.float32), axis=2)[:, :, ::-1].copy()
+        sc[:, :, 5:] = sc[:, :, 4:5]  # ties inside and across shards
+        ids = rng.integers(0, 1 << 40, size=(r, b, k)).astype(np.int64)
+        sc[3, :, 7:] = -np.inf
+        ids[3, :, 7:] = -1  # a short shard
+        es, ei = R.merge_shards(np.where(ids < 0, -np.inf, sc), ids, k)
+        gs, gi = merge_topk(torch.from_numpy(sc).cuda(), torch.from_numpy(ids).cuda(), k)
+        assert np.array_equal(gs.cpu().numpy(), es), (r, b, k)
+        assert np.array_equal(gi.cpu().numpy(), ei), (r, b, k)
 
 
 def test_sharded_searcher_packs_one_gather_buffer(native_lib):

