@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define VQA_VERSION 113 /* 0.1.13: vqa_index_options.sketch_regq (csrc/scan_regq.hip), .final_rescore, vqa_launch_info.scan_kernel, vqa_index_sketch_pause; 0.1.12: vqa_index_options.one_launch (vqa_index_search_host of a small fp16 shard is one kernel); 0.1.11: vqa_encoder_forward_host, device queries in vqa_index_search_host; 0.1.10: vqa_index_search_host; 0.1.9: vqa_index_options / vqa_index_create_ex, vqa_encoder_options / vqa_encoder_create_ex (no environment variable is read any more), vqa_launch_info.levels; 0.1.8: vqa_encoder_forward_hidden; 0.1.7: vqa_index_get_sketch_split; 0.1.6: vqa_index_sketch_stats, vqa_index_get_sketch_tile; 0.1.5: vqa_index_sketch_state; 0.1.4: VQA_INDEX_RESCORE_ROWS, vqa_index_device_bytes; 0.1.3: VQA_INDEX_SKETCH */
+#define VQA_VERSION 113 /* 0.1.13: vqa_index_options.sketch_regq (csrc/scan_regq.hip), .final_rescore, vqa_launch_info.scan_kernel, vqa_index_sketch_pause, vqa_index_search_filtered (detect it by its symbol); 0.1.12: vqa_index_options.one_launch (vqa_index_search_host of a small fp16 shard is one kernel); 0.1.11: vqa_encoder_forward_host, device queries in vqa_index_search_host; 0.1.10: vqa_index_search_host; 0.1.9: vqa_index_options / vqa_index_create_ex, vqa_encoder_options / vqa_encoder_create_ex (no environment variable is read any more), vqa_launch_info.levels; 0.1.8: vqa_encoder_forward_hidden; 0.1.7: vqa_index_get_sketch_split; 0.1.6: vqa_index_sketch_stats, vqa_index_get_sketch_tile; 0.1.5: vqa_index_sketch_state; 0.1.4: VQA_INDEX_RESCORE_ROWS, vqa_index_device_bytes; 0.1.3: VQA_INDEX_SKETCH */
 
 /* error codes */
 #define VQA_OK 0
@@ -208,6 +208,19 @@ int vqa_index_get_sketch_split(vqa_index* index, int64_t tile, float* out_c /* [
  * queueing them one behind the other.) */
 int vqa_index_search(vqa_index* index, const void* q, int32_t q_dtype, int32_t B, int32_t k, float* out_scores,
                      int64_t* out_ids, int64_t* out_pos_or_null, void* hip_stream);
+
+/* Filtered search: vqa_index_search restricted to the rows whose bit is set in allow_bits -- DEVICE memory, ceil(n / 32) uint32
+ * words, row position p allowed iff (allow_bits[p >> 5] >> (p & 31)) & 1; bits at positions >= n are ignored.  Same contract as
+ * vqa_index_search otherwise: exact top-k of the stored values among the allowed rows, best first, ties by position ascending,
+ * padded with (-inf, -1) when fewer than k rows are allowed (none allowed: all padding); 1 <= k <= VQA_MAX_K_TOTAL; any B;
+ * asynchronous on hip_stream; no allocation, no host synchronisation, capturable into a hipGraph (the bitmap's CONTENT is read
+ * on the device only, so a replay follows whatever the buffer holds at replay time).  A NULL or host allow_bits is VQA_EINVAL.
+ * Cost: the scan reads only the 256-row tiles that hold an allowed row (bytes = tiles touched x 256 x d x element size), once per
+ * 12 results of k.  The sketch is never used, and its pause state (vqa_index_sketch_state) is neither read nor changed.  On the
+ * shards whose exact paths end in the re-scoring arithmetic (vqa_index_options.final_rescore) this one does too: an all-ones
+ * bitmap returns the bits of vqa_index_search on the same handle. */
+int vqa_index_search_filtered(vqa_index* index, const void* q, int32_t q_dtype, int32_t B, int32_t k, const uint32_t* allow_bits,
+                              float* out_scores, int64_t* out_ids, int64_t* out_pos_or_null, void* hip_stream);
 
 /* The latency form of vqa_index_search for the reference's own calling pattern -- one question per call, limit = 1
  * (heavy_ranker.py:97-101): HOST pointers in and out, synchronous.  q_host [B, d] fp32 / fp16 host memory; normalize = 1 (fp32

@@ -92,6 +92,8 @@ struct vqa_index {
     float* thr_seed = nullptr;   // [256] the cascade's theta0 (k-th largest exact seed, MFMA arithmetic): kept for its exact fallback
     vqa_key* upper = nullptr;    // [256] last key returned per query (continuation passes of a search with k > 12)
     int* wide_flag = nullptr;    // 1 = the one-pass large-k result could not be verified: the gated continuation passes run
+    int* flt_tiles = nullptr;    // filtered search: [ceil(n / 256)] tiles holding an allowed row, then [1] their count, then
+                                 // [vqa_filter_chunks(n)] per-chunk counts of the compaction (filter.hip)
     // the exact paths' final re-scoring on large fp16 / fp32 shards (sketch.hip final_rescore_kernel): where the merge of an exact scan leaves its
     // rows before they are scored by the re-scoring arithmetic and re-ranked into the caller's arrays
     float* fin_scores = nullptr;   // [256][VQA_MAX_K_TOTAL]
@@ -229,6 +231,7 @@ extern "C" void vqa_index_destroy(vqa_index* ix) {
     if (ix->thr_seed) (void)hipFree(ix->thr_seed);
     if (ix->upper) (void)hipFree(ix->upper);
     if (ix->wide_flag) (void)hipFree(ix->wide_flag);
+    if (ix->flt_tiles) (void)hipFree(ix->flt_tiles);
     if (ix->fin_scores) (void)hipFree(ix->fin_scores);
     if (ix->fin_ids) (void)hipFree(ix->fin_ids);
     if (ix->fin_pos) (void)hipFree(ix->fin_pos);
@@ -555,6 +558,7 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
             hipMalloc((void**)&ix->thr_seed, VQA_QUERY_TILE * sizeof(float)) != hipSuccess ||
             hipMalloc((void**)&ix->upper, VQA_QUERY_TILE * sizeof(vqa_key)) != hipSuccess ||
             hipMalloc((void**)&ix->wide_flag, sizeof(int)) != hipSuccess ||
+            hipMalloc((void**)&ix->flt_tiles, ((size_t)tiles + 1 + vqa_filter_chunks(n)) * sizeof(int)) != hipSuccess ||
             ((dtype == VQA_F16 || dtype == VQA_F32) &&
              (hipMalloc((void**)&ix->fin_scores, (size_t)VQA_QUERY_TILE * VQA_MAX_K_TOTAL * 4) != hipSuccess ||
               hipMalloc((void**)&ix->fin_ids, (size_t)VQA_QUERY_TILE * VQA_MAX_K_TOTAL * 8) != hipSuccess ||
@@ -668,6 +672,7 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
             (void)hipMemset(ix->thr0, byte, VQA_QUERY_TILE * sizeof(float));
             (void)hipMemset(ix->thr_seed, byte, VQA_QUERY_TILE * sizeof(float));
             (void)hipMemset(ix->upper, byte, VQA_QUERY_TILE * sizeof(vqa_key));
+            (void)hipMemset(ix->flt_tiles, byte, ((size_t)((n + 255) / 256) + 1 + vqa_filter_chunks(n)) * sizeof(int));
             if (ix->sketch) {
                 (void)hipMemset(ix->qrow, byte, 5 * VQA_QUERY_TILE * sizeof(float));
                 (void)hipMemset(ix->qconst, byte, kSketchQRows * VQA_QUERY_TILE * sizeof(float));
@@ -1443,6 +1448,99 @@ static int search_impl(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B,
     if (sketch_call && !mirror_by_kernel)
         VQA_HIP_CHECK(hipMemcpyAsync(ix->sketch_flag_host, ix->sketch_flag, 5 * sizeof(int), hipMemcpyDeviceToHost, stream));
     return VQA_OK;
+}
+
+// ---- filtered search: the exact top-k among the rows whose bit is set in a device bitmap (vqa_index_search_filtered).
+// Plan: one compaction of the bitmap into the handle's tile list (filter.hip, device only), then per query tile the exact passes of
+// the unfiltered path -- one for k <= 12, ceil(k / 12) continuation passes below the last returned key beyond -- as MODE 3 launches
+// over the listed tiles, each merged by merge_partials.  The launch geometry depends on the shard only (grid = min(CUs, tiles)), so a
+// captured graph replays any selection.  The sketch is never used and its pause state is neither read nor changed: the bound speaks of
+// all rows, not of a selection.  Where the exact paths end in the re-scoring arithmetic (final_rescore_applies) this one does too, the
+// same way, so an all-ones bitmap returns the bits of vqa_index_search on the handle.
+static int filtered_impl(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B, int32_t k, const uint32_t* allow, float* out_scores,
+                         int64_t* out_ids, int64_t* out_pos_or_null, hipStream_t stream) {
+    const int max_k = vqa_score_topk_max_k(ix->dtype);
+    const int qeb = q_dtype == VQA_F32 ? 4 : 2;
+    const LaunchPlan p = plan_launch(ix, k);
+    const int tiles = (int)((ix->n + 255) / 256);
+    int* const list = ix->flt_tiles;
+    int* const count = ix->flt_tiles + tiles;
+    int rc = VQA_OK;
+    if (ix->n > 0 && (rc = vqa_launch_filter_tiles(allow, ix->n, list, count, count + 1, stream)) != VQA_OK) return rc;
+    FilterScanArgs f;
+    f.tiles = list;
+    f.count = count;
+    f.allow = allow;
+    f.nwords = (ix->n + 31) / 32;
+    const bool fin = final_rescore_applies(ix, p);
+    const int q_tiles = (B + VQA_QUERY_TILE - 1) / VQA_QUERY_TILE;
+    const int q_per = q_tiles > 1 ? (B + q_tiles - 1) / q_tiles : VQA_QUERY_TILE;
+    for (int q0 = 0; q0 < B; q0 += q_per) {
+        const int nq = B - q0 < q_per ? B - q0 : q_per;
+        float* os = out_scores + (size_t)q0 * k;
+        int64_t* oi = out_ids + (size_t)q0 * k;
+        int64_t* op = out_pos_or_null ? out_pos_or_null + (size_t)q0 * k : nullptr;
+        if (ix->n == 0) {  // empty shard: every slot is padding (as vqa_index_search)
+            VQA_HIP_CHECK(hipMemsetAsync(ix->partial, 0, (size_t)VQA_QUERY_TILE * max_k * sizeof(vqa_key), stream));
+            for (int done = 0; done < k; done += max_k) {
+                const int kk = k - done < max_k ? k - done : max_k;
+                if ((rc = vqa_launch_merge_partials(ix->partial, 1, max_k, nq, kk, ix->ids, ix->id_base, os, oi, op, nullptr, 1.0f, k, done, nullptr,
+                                                    false, nullptr, stream)) != VQA_OK)
+                    return rc;
+            }
+            continue;
+        }
+        const void* q_tile = reinterpret_cast<const char*>(q) + (size_t)q0 * ix->d * qeb;
+        if ((rc = vqa_launch_tile_rows(q_tile, q_dtype, 0, VQA_QUERY_TILE, nq, ix->d, ix->d_pad, ix->dtype, ix->scale, ix->q_stage, stream)) != VQA_OK)
+            return rc;
+        // as search_impl's exact passes: k + 2 rows of one pass, or the k rows of the continuation passes, re-scored at the end where fin
+        const int kx = fin && k + 2 <= max_k && ix->n >= k + 2 ? 2 : 0;
+        int64_t* const wide_pos = fin && k > max_k ? (op ? op : ix->fin_pos) : op;
+        const bool one_pass_fin = fin && k <= max_k;
+        for (int done = 0; done < k; done += max_k) {
+            const int kk = (k - done < max_k ? k - done : max_k) + kx;
+            ScoreTopkArgs a = exact_launch_args(ix, nq, kk);
+            a.upper = done > 0 ? ix->upper : nullptr;
+            a.grid = p.grid1;
+            a.filter = &f;
+            if (ix->timing && (rc = timing_event(ix, stream)) != VQA_OK) return rc;
+            if ((rc = vqa_launch_score_topk(ix->dtype, a, stream)) != VQA_OK) return rc;
+            if (ix->timing && (rc = timing_event(ix, stream)) != VQA_OK) return rc;
+            rc = vqa_launch_merge_partials(ix->partial, p.grid1, kk, nq, kk, ix->ids, ix->id_base, one_pass_fin ? ix->fin_scores : os,
+                                           one_pass_fin ? ix->fin_ids : oi, one_pass_fin ? ix->fin_pos : wide_pos, nullptr,
+                                           1.0f / (ix->scale * ix->scale), one_pass_fin ? kk : k, done, done + kk < k ? ix->upper : nullptr, true,
+                                           nullptr, stream);
+            if (rc != VQA_OK) return rc;
+            if (one_pass_fin && (rc = vqa_launch_final_rescore(ix->fin_pos, kk, nq, kk, k, ix->rows, nullptr, ix->q_stage, nullptr, ix->dtype, ix->d_pad,
+                                                               ix->ids, ix->id_base, os, oi, op, k, nullptr, stream)) != VQA_OK)
+                return rc;
+        }
+        if (fin && k > max_k &&
+            (rc = vqa_launch_final_rescore(wide_pos, k, nq, k, k, ix->rows, nullptr, ix->q_stage, nullptr, ix->dtype, ix->d_pad, ix->ids, ix->id_base,
+                                           os, oi, op, k, nullptr, stream)) != VQA_OK)
+            return rc;
+    }
+    return VQA_OK;
+}
+
+extern "C" int vqa_index_search_filtered(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B, int32_t k, const uint32_t* allow_bits,
+                                         float* out_scores, int64_t* out_ids, int64_t* out_pos_or_null, void* hip_stream) {
+    VQA_REQUIRE(ix, "vqa_index_search_filtered: index is null");
+    VQA_REQUIRE(q && out_scores && out_ids, "vqa_index_search_filtered: null pointer");
+    VQA_REQUIRE(allow_bits, "vqa_index_search_filtered: allow_bits is null");
+    VQA_REQUIRE(B >= 1, "vqa_index_search_filtered: B=%d", B);
+    VQA_REQUIRE(k >= 1 && k <= VQA_MAX_K_TOTAL, "vqa_index_search_filtered: k=%d outside [1, %d]", k, VQA_MAX_K_TOTAL);
+    VQA_REQUIRE(q_dtype == VQA_F32 || q_dtype == VQA_F16, "vqa_index_search_filtered: q_dtype %d is not f32/f16", q_dtype);
+    {
+        hipPointerAttribute_t attr;
+        const bool device = hipPointerGetAttributes(&attr, allow_bits) == hipSuccess && attr.type == hipMemoryTypeDevice;
+        if (!device) (void)hipGetLastError();
+        VQA_REQUIRE(device, "vqa_index_search_filtered: allow_bits is not device memory");
+    }
+    HandleBusy busy(ix->busy);
+    VQA_REQUIRE(busy.ok, "vqa_index_search_filtered: this index handle is in use by another host thread (one call at a time per handle)");
+    DeviceGuard guard(ix->device);
+    return filtered_impl(ix, q, q_dtype, B, k, allow_bits, out_scores, out_ids, out_pos_or_null, (hipStream_t)hip_stream);
 }
 
 // ---- diagnostics of the sketch search (bench.py prices a step's physical bytes from the pair counts; tests/test_gpu_sketch_bound.py

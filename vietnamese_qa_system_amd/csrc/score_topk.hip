@@ -24,6 +24,8 @@
 //   MODE 1 "main": all tiles, thresholds seeded; flushes per-workgroup sorted top-k lists for K2 to merge.
 //   (STAGE 1 is the same MODE 1 code under a second symbol: the first-stage launch of a two-stage search, capi.hip, so that
 //   a kernel trace keeps it apart from the main launch.)
+//   MODE 3 "filtered": MODE 1 over the tiles of a device-resident list (filter.hip), rows whose bit is clear in the caller's bitmap
+//                  masked out before the threshold test (vqa_index_search_filtered, capi.hip).
 #include <type_traits>
 #include <utility>
 
@@ -260,6 +262,14 @@ __device__ __forceinline__ vqa_key load_key_now(const vqa_key* base, int idx) {
     return v;
 }
 
+// MODE 3: one word of a workgroup-uniform address by a SCALAR load (the tile list, the bitmap).  SMEM loads count in lgkmcnt, not
+// vmcnt, so they leave the counted vmcnt waits of the LDS-DMA stream exact; `idx` is uniform (blockIdx, tile counters).
+__device__ __forceinline__ uint32_t sload_u32(const void* base, uint32_t idx) {
+    uint32_t v;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(base), "s"(idx * 4u) : "memory");
+    return v;
+}
+
 __device__ __forceinline__ bool append_candidate(const Lists& L, int q, float v, uint32_t pos, int spill) {
     const int slot = atomicAdd(&L.cnt[q], 1) & kCntMask;  // ds_add_rtn_u32
     if (slot < kCap) {
@@ -432,7 +442,8 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
     const int c = lane & 15;
     const int g = lane >> 4;
 
-    if (MODE == 1 && tid < kQ) {
+    constexpr bool kLists = MODE == 1 || MODE == 3;  // candidate lists in LDS, flushed for K2
+    if (kLists && tid < kQ) {
         L.thr[tid] = tid < nq ? (thr_init ? thr_init[tid] : -INFINITY) : INFINITY;
         L.cnt[tid] = 0;
     }
@@ -457,8 +468,20 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
         if (tid == 0) *sk_cnt = 0;
     }
 
-    const int first_tile = tile_begin + blockIdx.x;
-    const int ntile = first_tile < tile_end ? (tile_end - first_tile + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+    // MODE 3: this workgroup's tiles are entries blockIdx.x, blockIdx.x + grid, ... of the device list (`list_n` of them)
+    // (every use of the MODE 3 names below sits in an `if constexpr` branch: the other modes compile exactly as before)
+    [[maybe_unused]] FilterScanArgs flt;
+    auto tile_at = [&](int i) __attribute__((always_inline)) -> int {  // the workgroup's i-th tile of the list, i < ntile
+        return (int)sload_u32(flt.tiles, blockIdx.x + (uint32_t)i * gridDim.x);
+    };
+    int first_tile = tile_begin + blockIdx.x;
+    int ntile = first_tile < tile_end ? (tile_end - first_tile + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+    if constexpr (MODE == 3) {
+        flt = __builtin_bit_cast(FilterScanArgs, sk);
+        const int list_n = (int)sload_u32(flt.count, 0);
+        first_tile = (int)blockIdx.x < list_n ? tile_at(0) : 0;
+        ntile = (int)blockIdx.x < list_n ? (list_n - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+    }
     const int total = ntile * KT;  // K-steps of this workgroup, numbered kappa = ti * KT + kt
     // MODE 2: (max ||x_hi||, max ||x_lo||, 1 / scale) of every tile this workgroup scans, in LDS (the launcher bounds ntile by kSketchMaxTiles)
     constexpr bool kBeta = MODE == 2 && LOOP == 2;  // per-row form: alpha beta added per (query, row) in the tile epilogue
@@ -492,7 +515,11 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
         x_src += kOperandBytes;
         if (++i_kt == KT) {
             i_kt = 0;
-            x_src += tile_jump;
+            if constexpr (MODE == 3) {
+                if (ik < total) x_src = reinterpret_cast<const char*>(X) + (size_t)tile_at(ik / KT) * KT * kOperandBytes;
+            } else {
+                x_src += tile_jump;
+            }
         }
         i_dst += kOperandBytes;
         if (i_dst >= xring_lds + kXRingBytes) i_dst -= kXRingBytes;
@@ -640,6 +667,25 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
 #pragma unroll
                     for (int ni = 0; ni < 4; ++ni) acc[mi][ni][j] = dead ? __builtin_nanf("") : acc[mi][ni][j];
                 }
+        }
+    };
+    // MODE 3: rows whose bit is clear in the caller's bitmap never compete (NaN, as past the end).  The wave's 128 rows are words
+    // 4 wm .. 4 wm + 3 of the tile's 8 (uniform: scalar loads, none at or past nwords -- those rows lie past n and are NaN already);
+    // accumulator (mi, j) is bit 16 (mi & 1) + 4 g + j of word mi >> 1.
+    [[maybe_unused]] auto mask_filter = [&](f32x4 (&acc)[8][4], uint32_t row0) __attribute__((always_inline)) {
+        const long long w0 = (long long)(row0 >> 5) + 4 * wm;
+        uint32_t w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[i] = w0 + i < flt.nwords ? sload_u32(flt.allow, (uint32_t)(w0 + i)) : 0u;
+#pragma unroll
+        for (int mi = 0; mi < 8; ++mi) {
+            const uint32_t nib = w[mi >> 1] >> ((mi & 1) * 16 + g * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool dead = !((nib >> j) & 1u);
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni) acc[mi][ni][j] = dead ? __builtin_nanf("") : acc[mi][ni][j];
+            }
         }
     };
     // MODE 0: two sub-maxima per query and tile (one per row half wm) -> seeds [query][seed tile][2].  Each is the score
@@ -838,12 +884,14 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
     // ---- tile epilogue shared by the fp16 / fp32 loop forms: threshold test + appends (MODE 1) or sub-maxima (MODE 0).
     // `ext_stage`: an X ring stage that stays idle until every wave has passed the next workgroup barrier
     auto finish_tile = [&](f32x4 (&acc)[8][4], int ti, int ext_stage) __attribute__((always_inline)) {
-        const uint32_t row0 = ((uint32_t)first_tile + (uint32_t)ti * gridDim.x) * kTileRows;  // n < 2^32 rows
+        uint32_t row0 = ((uint32_t)first_tile + (uint32_t)ti * gridDim.x) * kTileRows;  // n < 2^32 rows
+        if constexpr (MODE == 3) row0 = (uint32_t)tile_at(ti) * kTileRows;
         if (MODE == 2) {
             sketch_epilogue(acc, row0, ti);
             return;
         }
         mask_ragged(acc, row0);
+        if constexpr (MODE == 3) mask_filter(acc, row0);
         if (MODE == 0) {
             seed_epilogue(acc, row0, ti);
             return;
@@ -988,6 +1036,7 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
                 if (++src_kt == KT) {
                     src_kt = 0;
                     if constexpr (kQ0) src = reinterpret_cast<const char*>(Qs);
+                    else if constexpr (MODE == 3) src = reinterpret_cast<const char*>(X) + (size_t)tile_at(n_issued / KT) * KT * kOperandBytes;
                     else src += tile_jump;
                 }
             }
@@ -1105,7 +1154,7 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
                 issue();                                                                                             \
                 owe = false;                                                                                         \
             }                                                                                                        \
-            if (MODE == 1 && LAST) owe = true;                                                                       \
+            if (kLists && LAST) owe = true;                                                                          \
             else issue();                                                                                            \
             if constexpr (kBeta && FIRST) { /* the tile's 256 betas -> LDS: one more LDS-DMA piece of ONE wave.  It sits in that wave's */ \
                 /* in-order vmcnt stream behind this K-step's pieces: the counted waits of the next three K-steps become stricter by  */ \
@@ -1196,7 +1245,11 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
             x_kt += 2;
             if (x_kt >= KT) {
                 x_kt -= KT;
-                xs += tile_jump;
+                if constexpr (MODE == 3) {
+                    if (xk < total) xs = reinterpret_cast<const char*>(X) + ((size_t)tile_at(xk / KT) * KT + x_kt) * kOperandBytes;
+                } else {
+                    xs += tile_jump;
+                }
             }
             xd += 2 * kOperandBytes;
             if (xd >= xring_lds + kXRingBytes) xd -= kXRingBytes;
@@ -1221,7 +1274,7 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
                 unsigned long long stamp_t[kStampSlots] = {};
 #endif
                 VQA_STAMP(0);
-                if (MODE == 1 && jj == 0 && ti > 0) compact_pass(L, wave, lane, k, k + (kCap - k + 1) / 2, kCap);
+                if (kLists && jj == 0 && ti > 0) compact_pass(L, wave, lane, k, k + (kCap - k + 1) / 2, kCap);
                 bool xi = false;
 #if !(VQA_ABLATE & 33)
                 if (kEarly) {
@@ -1248,7 +1301,7 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
                 VQA_STAMP(4);
                 block_barrier();
                 VQA_STAMP(5);
-                if (MODE == 1 && kEarly && jj == 0 && ti > 0) repair(false, fq_other);  // group B's E slot just ended
+                if (kLists && kEarly && jj == 0 && ti > 0) repair(false, fq_other);  // group B's E slot just ended
                 // ---- M slot: nothing but the 32 MFMAs
                 if (jj == 0) {
 #pragma unroll
@@ -1271,11 +1324,13 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
                 block_barrier();
                 VQA_STAMP(7);
                 VQA_STAMP_FLUSH(jj);
-                if (MODE == 1 && !kEarly && jj == P - 1) repair(false, fq_other);  // group A's E slot just ended
+                if (kLists && !kEarly && jj == P - 1) repair(false, fq_other);  // group A's E slot just ended
             }
             // ---- E slot
-            row0 = ((uint32_t)first_tile + (uint32_t)ti * gridDim.x) * kTileRows;
+            if constexpr (MODE == 3) row0 = (uint32_t)tile_at(ti) * kTileRows;
+            else row0 = ((uint32_t)first_tile + (uint32_t)ti * gridDim.x) * kTileRows;
             mask_ragged(acc, row0);
+            if constexpr (MODE == 3) mask_filter(acc, row0);
             if (MODE == 0) {
                 seed_epilogue(acc, row0, ti);
                 block_barrier();
@@ -1287,10 +1342,12 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
         }
         if (kEarly) {  // group B's last E slot
             block_barrier();
-            if (MODE == 1) repair(false, fq_other);
+            if (kLists) repair(false, fq_other);
         }
     };
 
+    // MODE 3: a workgroup whose share of the list is empty issues no load at all (not even the ring's prologue); its lists flush empty
+    if (MODE != 3 || ntile > 0) {
     if constexpr (kStagger) {
         if (grp) stagger_loop(std::false_type{});
         else stagger_loop(std::true_type{});
@@ -1300,6 +1357,7 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
     } else {
         if (grp) tile_loop(std::false_type{});
         else tile_loop(std::true_type{});
+    }
     }
 
 #ifdef VQA_STAMPS
@@ -1397,6 +1455,23 @@ static int launch_sketch(const ScoreTopkArgs& a, int KT, int lds, hipStream_t st
 
 int vqa_score_topk_sketch_max_tiles() { return kSketchMaxTiles; }
 
+// MODE 3: the filtered scan over the tiles of a device list (fp16 on the slot loop, fp8 on the stagger loop, fp32 on the tile loop)
+template <int DT>
+static int launch_filtered(const ScoreTopkArgs& a, int KT, int lds, hipStream_t stream) {
+    static VqaPerDeviceOnce once;
+    int rc = once.run([&](int) -> int {
+        VQA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(score_topk_kernel<3, DT, 0, 0>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        return VQA_OK;
+    });
+    if (rc != VQA_OK) return rc;
+    hipLaunchKernelGGL((score_topk_kernel<3, DT, 0, 0>), dim3(a.grid), dim3(kThreads), lds, stream, a.x, a.q, a.thr_init, a.upper, a.partial,
+                       (long long)a.n, KT, a.nq, a.k, 0, 0, nullptr, a.row_lists > 0 ? a.row_lists : a.grid, a.list_offset, 2,
+                       vqa_filter_carrier(*a.filter));
+    VQA_HIP_CHECK(hipGetLastError());
+    return VQA_OK;
+}
+
 int vqa_launch_score_topk(int dtype, const ScoreTopkArgs& a, hipStream_t stream) {
     if (a.sketch) {
         VQA_REQUIRE(dtype == VQA_I8_SKETCH && a.d_pad % (2 * kRowBytes) == 0, "score_topk: sketch scan over %d-element rows", a.d_pad);
@@ -1417,6 +1492,18 @@ int vqa_launch_score_topk(int dtype, const ScoreTopkArgs& a, hipStream_t stream)
                 "score_topk: padded row of %d elements x %d B is not a multiple of %d B", a.d_pad, esize, 2 * kRowBytes);
     VQA_REQUIRE(a.k >= 1 && a.k <= kMaxK, "score_topk: k=%d outside [1, %d]", a.k, kMaxK);
     VQA_REQUIRE(a.nq >= 1 && a.nq <= kQ, "score_topk: nq=%d outside [1, %d]", a.nq, kQ);
+    if (a.filter) {
+        const long long tiles = (a.n + kTileRows - 1) / kTileRows;
+        VQA_REQUIRE(a.filter->tiles && a.filter->count && a.filter->allow && a.filter->nwords == (a.n + 31) / 32,
+                    "score_topk: incomplete filter arguments");
+        VQA_REQUIRE(a.grid >= 1 && a.grid <= tiles && !a.seed_only && !a.gate, "score_topk: bad filtered launch (%d workgroups, %lld tiles)",
+                    a.grid, tiles);
+        const int KT = a.d_pad * esize / kRowBytes;
+        const int lds = vqa_score_topk_lds_bytes(dtype, a.k);
+        if (dtype == VQA_F16) return launch_filtered<VQA_F16>(a, KT, lds, stream);
+        if (dtype == VQA_FP8_E4M3) return launch_filtered<VQA_FP8_E4M3>(a, KT, lds, stream);
+        return launch_filtered<VQA_F32>(a, KT, lds, stream);
+    }
     VQA_REQUIRE(a.grid >= 1 && a.tile_end > a.tile_begin, "score_topk: empty launch");
     VQA_REQUIRE(a.seeds_per_tile == 2 || a.seeds_per_tile == 8, "score_topk: %d seeds per tile", a.seeds_per_tile);
     VQA_REQUIRE(a.grid <= a.tile_end - a.tile_begin, "score_topk: %d workgroups for %d tiles (every workgroup needs a tile)", a.grid,

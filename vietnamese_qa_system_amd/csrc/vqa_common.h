@@ -139,6 +139,17 @@ struct SketchScanArgs {
     int cap = 0;
 };
 
+// MODE 3 of the scoring kernel (the filtered scan): the tiles it takes come from a device-resident list, and a row whose bit is clear
+// in the caller's bitmap never reaches the threshold test.  The kernel's signature stays that of MODEs 0-2 -- and with it the code of
+// every one of their instantiations -- so these pointers travel in the bytes of its SketchScanArgs parameter (vqa_filter_carrier).
+struct FilterScanArgs {
+    const int* tiles = nullptr;      // [tiles] ascending tiles holding at least one allowed row (filter.hip) ...
+    const int* count = nullptr;      // ... and how many there are (device: the host never learns it)
+    const uint32_t* allow = nullptr; // [nwords] the caller's row bitmap, bit p & 31 of word p >> 5
+    long long nwords = 0;            // ceil(n / 32): no word at or past it is read
+    unsigned char unused[32] = {};
+};
+
 // ---- kernel launchers implemented in the .hip files ---------------------------------------------------------
 struct ScoreTopkArgs {
     const void* x = nullptr;  // index rows in TILED layout (convert.hip): ceil(n/256) tiles x (d_pad/32) blocks of 16 KiB
@@ -165,7 +176,14 @@ struct ScoreTopkArgs {
     bool seed_only = false;  // MODE 0: writes seeds_per_tile sub-maxima per query and tile to `partial` as [query][tile - tile_begin][.]
     int32_t seeds_per_tile = 2;  // 2 (one per 128-row half) or 8 (one per 32-row group: shards of a few tiles, where 2 per tile
                                  // are fewer than k values and leave the thresholds at -inf)
+    const FilterScanArgs* filter = nullptr;  // not null: MODE 3 over the listed tiles (tile_begin / tile_end unused; grid <= tiles of the shard)
 };
+static_assert(sizeof(FilterScanArgs) == sizeof(SketchScanArgs), "MODE 3 carries its arguments in the bytes of SketchScanArgs");
+__host__ __device__ inline SketchScanArgs vqa_filter_carrier(const FilterScanArgs& f) { return __builtin_bit_cast(SketchScanArgs, f); }
+// filter.hip: the ascending list of the tiles of an n-row shard that hold an allowed row, and its length, from the row bitmap
+// (two launches; `chunk_cnt`: vqa_filter_chunks(n) ints of scratch)
+int vqa_filter_chunks(int64_t n);
+int vqa_launch_filter_tiles(const uint32_t* allow, int64_t n, int* tiles, int* count, int* chunk_cnt, hipStream_t stream);
 int vqa_launch_score_topk(int dtype, const ScoreTopkArgs& a, hipStream_t stream);
 // scan_regq.hip: the sketch scan with the query operand resident in registers (rows of 768 / 384 one-byte elements, no per-row betas)
 bool vqa_sketch_regq_applies(const ScoreTopkArgs& a);

@@ -34,6 +34,7 @@ import torch.distributed as dist
 from . import _native as N
 from . import docstore
 from .index import _STORE_NP, DeviceIndex, resolve_dtype
+from .rowfilter import RowFilter
 from .sharded import ShardedSearcher, shard_bounds
 from .sparse import BM25Index, combine
 
@@ -97,6 +98,8 @@ class Embeddings:
         self._docs_mem: Optional[dict] = None   # device-level id -> document (lookup at search time)
         self._docs_rows: Optional[list] = None  # [(device-level id, document)] of the rows this rank was given
         self._lo = 0                            # first global row of this rank's shard
+        self._shard_ids: Optional[np.ndarray] = None  # host copy of this shard's id vector (filters by id / by document field)
+        self._allow: Optional[RowFilter] = None  # the shard's filter of the search in progress (_local_search)
         self.load_stats: Optional[dict] = None  # filled by load(): bytes, seconds, GB/s of the file -> HBM stream
         self.n = 0
         self.d = 0
@@ -279,6 +282,7 @@ class Embeddings:
                 self._index.set_rows(c0 - lo, rows, dev_ids[c0 - lo:c1 - lo] if dev_ids is not None else None, normalize=normalize)
         self._searcher = ShardedSearcher(self._local_search, None, self.group)
         self.n, self.d, self._lo = n, d, lo
+        self._shard_ids = np.asarray(dev_ids, dtype=np.int64) if dev_ids is not None else None
         self._docs_db = None
         self._docs_rows = self._docs_mem = None
         if documents is not None:
@@ -291,7 +295,102 @@ class Embeddings:
             self._docs_mem = dict(self._docs_rows)
 
     def _local_search(self, q: torch.Tensor, k: int, out_s: torch.Tensor, out_i: torch.Tensor) -> None:
-        self._index.search(q, k, out=(out_s, out_i))
+        self._index.search(q, k, out=(out_s, out_i), allow=self._allow)
+
+    # ---- filters (search(..., filter=...)) ----------------------------------------------------------------------------
+    def _device_ids_of(self, flt) -> np.ndarray:
+        """What the device reports for the rows a filter selects (global row positions for string ids): ``flt`` is an iterable of
+        external ids (unknown ones are ignored) or a ``{field: value | list / tuple / set of values}`` dict matched against the stored
+        documents -- in memory after ``index(content=True)``, else one ``SELECT id FROM documents WHERE <field> IN (...)`` per field."""
+        if isinstance(flt, dict):
+            keys = None
+            for field, want in flt.items():
+                vals = list(want) if isinstance(want, (list, tuple, set, frozenset)) else [want]
+                got = self._doc_ids_where(str(field), vals)
+                keys = got if keys is None else np.intersect1d(keys, got)
+            return keys if keys is not None else np.zeros(0, np.int64)
+        wanted = list(flt)
+        if self._host_ids is not None:
+            pos = getattr(self, "_host_pos", None)
+            if pos is None or len(pos) != len(self._host_ids):
+                pos = self._host_pos = {h: p for p, h in enumerate(self._host_ids)}
+            return np.asarray([pos[i] for i in wanted if i in pos], dtype=np.int64)
+        return np.asarray([int(i) for i in wanted if isinstance(i, (int, np.integer)) and not isinstance(i, bool)], dtype=np.int64)
+
+    def _doc_ids_where(self, field: str, values: list) -> np.ndarray:
+        if self._docs_rows is not None:
+            if not any(field in doc for _, doc in self._docs_rows):
+                raise ValueError(f"filter field {field!r}: no stored document has it")
+            vs = set(values)
+            return np.asarray(sorted({key for key, doc in self._docs_rows if field in doc and doc[field] in vs}), dtype=np.int64)
+        if self._docs_db is not None:
+            import sqlite3
+            column = "doc" if field == "text" else field
+            conn = sqlite3.connect(self._docs_db)
+            try:
+                cols = {r[1] for r in conn.execute("PRAGMA table_info(documents)")}
+                if column not in cols or column == "id":
+                    raise ValueError(f"filter field {field!r}: the document store holds {sorted(cols - {'id'})}")
+                out = []
+                for c0 in range(0, max(len(values), 1), 900):
+                    chunk = values[c0:c0 + 900]
+                    if not chunk:
+                        break
+                    marks = ",".join("?" * len(chunk))
+                    out += [int(r[0]) for r in conn.execute(f"SELECT id FROM documents WHERE {column} IN ({marks})", chunk)]
+            finally:
+                conn.close()
+            return np.unique(np.asarray(out, dtype=np.int64))
+        raise ValueError("a filter by document field needs stored documents (content=True)")
+
+    def _shard_mask(self, device_ids: np.ndarray) -> np.ndarray:
+        """bool [rows of this shard]: the shard rows whose device-reported id is in ``device_ids``."""
+        n_loc = self._index.n
+        if self._shard_ids is not None:
+            return np.isin(self._shard_ids, device_ids)
+        m = np.zeros(n_loc, dtype=bool)
+        p = np.asarray(device_ids, dtype=np.int64) - self._index.id_base
+        m[p[(p >= 0) & (p < n_loc)]] = True
+        return m
+
+    def _resolve_filter(self, flt, need_global: bool):
+        """-> (this shard's RowFilter on its device, bool [n] mask over global row positions or None unless ``need_global``)."""
+        lo, hi = self._lo, self._lo + self._index.n
+        if isinstance(flt, RowFilter):
+            if flt.n == self.n:
+                glob = flt.mask().cpu().numpy() if need_global else None
+                local = flt.slice(lo, hi) if (lo, hi) != (0, self.n) else flt
+            elif flt.n == hi - lo and self.world == 1:
+                local, glob = flt, (flt.mask().cpu().numpy() if need_global else None)
+            else:
+                raise ValueError(f"a RowFilter of {flt.n} rows for an index of {self.n}")
+            return local.to(self.device), glob
+        dids = self._device_ids_of(flt)
+        local = RowFilter.from_mask(self._shard_mask(dids), device=self.device)
+        glob = None
+        if need_global:
+            if self._row_ids is None:
+                raise ValueError("this index cannot map a filter onto the keyword half (hybrid search needs the whole corpus' ids)")
+            glob = np.isin(self._row_ids, dids)
+        return local, glob
+
+    def _filtered(self, queries, limit: int, flt) -> List[list]:
+        """batchsearch with a filter: always the device path (the encoder's device output for text queries), one sync."""
+        q = self._query_vectors(queries)
+        if q.shape[1] != self.d:
+            raise ValueError(f"query dimension {q.shape[1]} != index dimension {self.d}")
+        texts = list(queries) if not isinstance(queries, (np.ndarray, torch.Tensor)) and len(queries) and isinstance(queries[0], str) else None
+        hybrid = self.hybrid and self._sparse is not None and texts is not None and 0.0 < self.weights < 1.0
+        local, glob = self._resolve_filter(flt, need_global=hybrid)
+        if hybrid:
+            return self._hybrid(q, texts, limit, allow=(local, glob))
+        self._allow = local
+        try:
+            scores, ids = self._searcher.search(q, limit)
+        finally:
+            self._allow = None
+        torch.cuda.current_stream(q.device).synchronize()
+        return self._format(scores.cpu().numpy(), ids.cpu().numpy())
 
     def count(self) -> int:
         return self.n
@@ -321,13 +420,20 @@ class Embeddings:
             v = out
         return v
 
-    def batchsearch(self, queries, limit: int = 3) -> List[list]:
-        """txtai ``batchsearch``: one result list per query; ``queries`` is a list of strings or a [B, d] array."""
+    def batchsearch(self, queries, limit: int = 3, filter=None) -> List[list]:
+        """txtai ``batchsearch``: one result list per query; ``queries`` is a list of strings or a [B, d] array.  ``filter``: search
+        only part of the corpus -- an iterable of ids, a ``{field: value(s)}`` dict matched against the stored documents (e.g.
+        ``{"source": "x"}``), or a :class:`RowFilter` over the corpus' row positions; the result is the exact top ``limit`` among
+        those rows (fewer only when fewer are selected)."""
         if self._index is None:
             raise RuntimeError("the index is empty: call index()/load() first")
         if isinstance(queries, str):
             queries = [queries]
         limit = int(limit)
+        if filter is not None:
+            if isinstance(queries, np.ndarray) and queries.dtype == np.float64:
+                queries = queries.astype(np.float32)
+            return self._filtered(queries, limit, filter)
         # host-resident vector queries against one shard (the reference asks one question per call, heavy_ranker.py:97-101): the
         # library's latency entry -- one call, no torch tensor on the way in or out
         if isinstance(queries, np.ndarray) and queries.dtype == np.float64:
@@ -441,7 +547,7 @@ class Embeddings:
         scores, out_ids = self._index.search_host(q, int(limit), normalize=self.normalize)
         return self._format(scores, out_ids)[0]
 
-    def _hybrid(self, q: torch.Tensor, texts: List[str], limit: int, host_results: bool = False) -> List[list]:
+    def _hybrid(self, q: torch.Tensor, texts: List[str], limit: int, host_results: bool = False, allow=None) -> List[list]:
         """txtai's hybrid search [recalled, see sparse.py]: 10 x limit candidates from each half, per-id convex combination
         ``weights * dense + (1 - weights) * bm25`` (BM25 normalised to 0..1), best ``limit``.  ``host_results``: ``q`` is the device output
         of the encoder's host entry and the dense candidates come through the index's host-result entry (one question: one kernel)."""
@@ -452,26 +558,32 @@ class Embeddings:
             sparse_all = [[(int(self._row_ids[r]), s) for r, s in self._sparse.search(text, cand)] for text in texts]
             ds, di = self._index.search_host(q, cand, normalize=self.normalize)
         else:
-            scores, ids = self._searcher.search(q, cand)
+            # a filter (allow = (this shard's RowFilter, global row mask)) restricts both halves before their top-`cand` cuts
+            self._allow = allow[0] if allow is not None else None
+            try:
+                scores, ids = self._searcher.search(q, cand)
+            finally:
+                self._allow = None
             torch.cuda.current_stream(q.device).synchronize()
             ds, di = scores.cpu().numpy(), ids.cpu().numpy()
         out_s = np.full((len(texts), limit), -np.inf, dtype=np.float32)
         out_i = np.full((len(texts), limit), -1, dtype=np.int64)
         for b, text in enumerate(texts):
             dense = [(int(i), float(s)) for i, s in zip(di[b], ds[b]) if i >= 0 and s > 0]  # txtai drops dense scores <= 0
-            sparse = sparse_all[b] if sparse_all is not None else [(int(self._row_ids[r]), s) for r, s in self._sparse.search(text, cand)]
+            sparse = sparse_all[b] if sparse_all is not None else [
+                (int(self._row_ids[r]), s) for r, s in self._sparse.search(text, cand, allow=allow[1] if allow is not None else None)]
             for j, (uid, sc) in enumerate(combine(dense, sparse, limit, self.weights, self._sparse.normalize)):
                 out_i[b, j], out_s[b, j] = uid, sc
         return self._format(out_s, out_i)
 
-    def search(self, query: Query, limit: int = 3) -> list:
-        """``heavy_ranker.py:98``: the ``limit`` best documents for one query, best first."""
+    def search(self, query: Query, limit: int = 3, filter=None) -> list:
+        """``heavy_ranker.py:98``: the ``limit`` best documents for one query, best first (``filter``: see :meth:`batchsearch`)."""
         if not isinstance(query, str):
             arr = query if isinstance(query, (np.ndarray, torch.Tensor)) else np.asarray(query, dtype=np.float32)
             if arr.ndim != 1:
                 raise ValueError("search() takes ONE query (a string or a 1-D vector); use batchsearch() for several")
             query = arr
-        return self.batchsearch([query] if isinstance(query, str) else query[None, :], limit)[0]
+        return self.batchsearch([query] if isinstance(query, str) else query[None, :], limit, filter=filter)[0]
 
     def _format(self, scores: np.ndarray, ids: np.ndarray) -> List[list]:
         keep = ids >= 0
@@ -626,6 +738,7 @@ class Embeddings:
         self.load_stats = self._stream_rows(vec_path, np_dtype, lo, hi, d, ids)
         self._searcher = ShardedSearcher(self._local_search, None, self.group)
         self.n, self.d, self._lo = n, d, lo
+        self._shard_ids = ids
         db = os.path.join(path, DOCS_FILE)
         self._docs_db = db if os.path.isfile(db) else None
         self._docs_mem = self._docs_rows = None

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .rowfilter import RowFilter
 
 RESCORE_COPY_MAX_BYTES = 32 << 30  # rows of up to 32 GiB get the row-major re-scoring copy by default (DeviceIndex)
 _SRC_DTYPE = {torch.float32: N.VQA_F32, torch.float16: N.VQA_F16}
@@ -193,13 +194,25 @@ class DeviceIndex:
         return self.n
 
     # -- search --------------------------------------------------------------------------------------------------
+    def row_filter(self, positions=None, mask=None) -> RowFilter:
+        """The device bitmap of a filtered search (:meth:`search` ``allow=``), built once from shard-local row ``positions`` or a
+        bool / uint8 ``mask`` [n] (host or device) and reusable across searches without a new upload."""
+        if (positions is None) == (mask is None):
+            raise ValueError("row_filter takes exactly one of positions= and mask=")
+        if mask is not None:
+            if int(mask.shape[0]) != self.n:
+                raise ValueError(f"a row mask of this shard has {self.n} entries, got {int(mask.shape[0])}")
+            return RowFilter.from_mask(mask, device=self.device)
+        return RowFilter.from_positions(self.n, positions, device=self.device)
+
     def search(self, queries: torch.Tensor, k: int, *, return_positions: bool = False,
-               out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+               out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, allow: Optional[RowFilter] = None
                ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
         """``queries`` [B, d] fp32/fp16 cuda tensor -> (scores [B, k] fp32, ids [B, k] int64[, positions]), best first,
         ties by row position; slots beyond the shard's row count hold (-inf, -1).  Asynchronous on the current stream.
         ``out`` = (scores, ids): contiguous [B, k] float32 / int64 tensors on this device to write into (the sharded
-        searcher passes views of its all-gather send buffer)."""
+        searcher passes views of its all-gather send buffer).  ``allow``: a :class:`RowFilter` of this shard (:meth:`row_filter`):
+        the exact top-k among its rows only (``vqa_index_search_filtered``), padded with (-inf, -1) past the rows it allows."""
         if not self._handle.value:
             raise RuntimeError("index is closed")
         dev = torch.device("cuda", self.device)
@@ -216,15 +229,25 @@ class DeviceIndex:
             for t, dt in ((scores, torch.float32), (ids, torch.int64)):
                 if t.dtype != dt or tuple(t.shape) != (b, k) or t.device != dev or not t.is_contiguous():
                     raise ValueError(f"out tensors must be contiguous [{b}, {k}] float32 / int64 on {dev}")
+        if allow is not None:
+            if not isinstance(allow, RowFilter) or allow.n != self.n:
+                raise ValueError(f"allow must be a RowFilter of this shard's {self.n} rows")
+            if allow.bits.device != dev:
+                raise ValueError(f"the RowFilter lives on {allow.bits.device}, the shard on {dev}: build it with row_filter()")
         with torch.cuda.device(dev):
             if out is None:
                 scores = torch.empty((b, k), dtype=torch.float32, device=dev)
                 ids = torch.empty((b, k), dtype=torch.int64, device=dev)
             pos = torch.empty((b, k), dtype=torch.int64, device=dev) if return_positions else None
             stream = torch.cuda.current_stream(dev).cuda_stream
-            N.check(self._lib.vqa_index_search(self._handle, q.data_ptr(), _SRC_DTYPE[q.dtype], b, int(k), scores.data_ptr(),
-                                               ids.data_ptr(), pos.data_ptr() if pos is not None else None, stream),
-                    "vqa_index_search")
+            if allow is not None:
+                N.check(self._lib.vqa_index_search_filtered(self._handle, q.data_ptr(), _SRC_DTYPE[q.dtype], b, int(k), allow.bits.data_ptr(),
+                                                            scores.data_ptr(), ids.data_ptr(), pos.data_ptr() if pos is not None else None,
+                                                            stream), "vqa_index_search_filtered")
+            else:
+                N.check(self._lib.vqa_index_search(self._handle, q.data_ptr(), _SRC_DTYPE[q.dtype], b, int(k), scores.data_ptr(),
+                                                   ids.data_ptr(), pos.data_ptr() if pos is not None else None, stream),
+                        "vqa_index_search")
         return scores, ids, pos
 
     def search_host(self, queries, k: int, *, normalize: bool = False, return_positions: bool = False):

@@ -94,8 +94,9 @@ class BM25Index:
         return int(self.doclen.shape[0])
 
     # ---- search -----------------------------------------------------------------------------------------------------
-    def search(self, query: str, limit: int) -> List[Tuple[int, float]]:
-        """``[(row position, score)]``, best first (ties by row position), at most ``limit`` rows with a score > 0."""
+    def search(self, query: str, limit: int, allow: Optional[np.ndarray] = None) -> List[Tuple[int, float]]:
+        """``[(row position, score)]``, best first (ties by row position), at most ``limit`` rows with a score > 0.  ``allow``: bool
+        [n] row mask (a filtered search): the other rows score 0 before the cut, so they never appear."""
         n = len(self)
         if n == 0 or limit <= 0:
             return []
@@ -107,6 +108,11 @@ class BM25Index:
             lo, hi = self.indptr[tid], self.indptr[tid + 1]
             rows = self.docs[lo:hi]
             acc[rows] += self._score(self.tf[lo:hi], self.idf[tid], self.doclen[rows]).astype(np.float32)
+        if allow is not None:
+            allow = np.asarray(allow, dtype=bool)
+            if allow.shape != (n,):
+                raise ValueError(f"allow must be a bool [{n}] row mask")
+            acc[~allow] = 0
         hit = np.flatnonzero(acc > 0)
         if hit.size == 0:
             return []
