@@ -102,8 +102,8 @@ typedef struct vqa_index_options {
                                    * from which the two-stage / sketch plan applies; 0: never.  Given explicitly (tests at small sizes), the
                                    * profitability pause is off unless sketch_profit is given too */
     int32_t stage_pct;            /* [10] share of the first stage, percent (1..50) */
-    int32_t f16_loop;             /* [0] fp16 K loop: 0 anti-phase slots, 1 K-step pairs, 2 pairs for the main launch of a two-stage search */
-    int32_t sketch_cascade;       /* [1] cascade of bounds; 0: round 3's form with an exact first stage (k <= 12) */
+    int32_t f16_loop;             /* [0] retired (was the fp16 K loop; measured slower): any other value is VQA_EINVAL */
+    int32_t sketch_cascade;       /* [1] retired (0 was round 3's sketch form with an exact first stage): any other value is VQA_EINVAL */
     int32_t sketch_rotate;        /* [1] sketch cut from sign-flipped, block-Hadamard-rotated rows */
     int32_t sketch_center;        /* [1] ... of centred rows (needs the rotation) */
     int32_t sketch_split;         /* [1] slack term of the bound split along the centre direction */

@@ -1,5 +1,5 @@
-"""Dev helper: A/B of index options (named as rounds 1-4 named their environment switches: VQA_F16_LOOP, VQA_STAGE_MIN, ... -> scripts/_options.py), interleaved rounds in
-ONE process on one device (guide rule 24): `python scripts/ab_loops.py VQA_F16_LOOP=0 VQA_F16_LOOP=1 [--n rows] [--rounds R]`.
+"""Dev helper: A/B of index options (named as rounds 1-4 named their environment switches: VQA_STAGE_MIN, VQA_SKETCH_SX, ... -> scripts/_options.py), interleaved rounds in
+ONE process on one device (guide rule 24): `python scripts/ab_loops.py VQA_SKETCH_SX=5 VQA_SKETCH_SX=6 [--n rows] [--rounds R]`.
 Every variant is its own index over the same synthetic shard; per variant: median / min step and main-launch time."""
 import argparse, os, sys
 import numpy as np
@@ -9,7 +9,7 @@ from vietnamese_qa_system_amd.index import DeviceIndex
 from _options import options as _options
 
 ap = argparse.ArgumentParser()
-ap.add_argument("variants", nargs="+", help="comma-separated NAME=VALUE settings per variant, e.g. VQA_F16_LOOP=1,VQA_STAGE_MIN=0")
+ap.add_argument("variants", nargs="+", help="comma-separated NAME=VALUE settings per variant, e.g. VQA_SKETCH_SX=6,VQA_STAGE_MIN=0")
 ap.add_argument("--n", type=int, default=10_000_000)
 ap.add_argument("--d", type=int, default=768)
 ap.add_argument("--b", type=int, default=256)

@@ -55,6 +55,17 @@ int main() {
         bad_o = o;
         bad_o.flags = 0xF0;
         EXPECT(vqa_index_create_ex(&ix, 0, 10, 8, VQA_F16, nullptr, VQA_F16, nullptr, 0, &bad_o) == VQA_EINVAL);
+        // retired forms: the fields stay in the struct, only their defaults are accepted
+        for (int loop : {1, 2}) {
+            bad_o = o;
+            bad_o.f16_loop = loop;
+            EXPECT(vqa_index_create_ex(&ix, 0, 10, 8, VQA_F16, nullptr, VQA_F16, nullptr, 0, &bad_o) == VQA_EINVAL && ix == nullptr);
+            EXPECT(strstr(vqa_last_error(), "f16_loop") != nullptr);
+        }
+        bad_o = o;
+        bad_o.sketch_cascade = 0;
+        EXPECT(vqa_index_create_ex(&ix, 0, 10, 8, VQA_F16, nullptr, VQA_F16, nullptr, 0, &bad_o) == VQA_EINVAL && ix == nullptr);
+        EXPECT(strstr(vqa_last_error(), "sketch_cascade") != nullptr);
         // an OLDER caller's shorter struct: the fields it does not know keep their defaults (only the prefix is read)
         vqa_index_options shorter = o;
         shorter.struct_size = 16;

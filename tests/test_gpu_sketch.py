@@ -328,25 +328,6 @@ def test_row_major_rescoring_copy_changes_no_bit(native_lib, monkeypatch, dtype,
     assert p1[0, :3].tolist() == [5, 70_000, n - 1] and len(set(s1[0, :3].tolist())) == 1
 
 
-def test_first_form_with_an_exact_first_stage_still_agrees(native_lib, monkeypatch):
-    """VQA_SKETCH_CASCADE=0 keeps the round's first form of the search (exact fp16 first stage -> theta -> one sketch scan) as an
-    A / B switch: same rows and bit-equal scores as the cascade (every returned score comes from the same re-scoring kernel)."""
-    n, d, b, k = 210_000, 128, 50, 10
-    rng = np.random.default_rng(4)
-    x, q = _unit(rng, n, d), _unit(rng, b, d)
-    x[[7, 65_536, n - 2]] = x[7]
-    q[0] = x[7]
-    cascade = _index(x, monkeypatch, sketch=True)
-    set_option(monkeypatch, "VQA_SKETCH_CASCADE", "0")
-    first = _index(x, monkeypatch, sketch=True)
-    s0, _, p0 = _search(cascade, q, k)
-    s1, _, p1 = _search(first, q, k)
-    cascade.close()
-    first.close()
-    assert np.array_equal(p0, p1) and np.array_equal(s0, s1)
-    assert p0[0, :3].tolist() == [7, 65_536, n - 2]
-
-
 @pytest.mark.parametrize("b", [1, 3])
 def test_one_query_with_thousands_of_candidates_stays_on_the_sketch(native_lib, monkeypatch, b):
     """A single query whose neighbourhood holds 5000 near-duplicates scattered over the shard: every one of them is a candidate.

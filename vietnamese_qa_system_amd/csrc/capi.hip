@@ -74,7 +74,6 @@ struct vqa_index {
                                // crossover between 1M rows, +1 % step time, and 2M rows, -2 %; options.stage_min_tiles: dev /
                                // test override, 0 disables); the first stage takes stage_pct % of the tiles (options.stage_pct)
     int stage_pct = 10;
-    int f16_loop = 0;  // fp16 K loop: 0 = anti-phase slots (two barriers per K-step), 1 = K-step pairs on the stagger loop (options.f16_loop)
     // workspace (allocated once; search never allocates)
     void* q_stage = nullptr;     // one 256-row tile in TILED layout
     void* q_rm = nullptr;        // ... and row-major (sketch shards with the re-scoring copy: what rescore_kernel reads)
@@ -126,7 +125,6 @@ struct vqa_index {
                                             // (profiles/r04_profit_probe.txt, the set measured with the radix selections): the sketch search is level
                                             // with the exact forms over a wide band and loses clearly where pairs > 0.75 n - 4e5; the f32 MFMA scan of
                                             // fp32 shards is 16x slower: 4 n.  options.sketch_profit sets the factor, 0: never
-    long long* stage_pos = nullptr;         // [256][max_k] row positions of the first stage's top-k
     float* mu = nullptr;                    // [d_pad8] centre of the shard (mean of the rows of its first fill), subtracted before the sketch
     float* wdir = nullptr;                  // [d_pad8] (behind mu, same allocation) w = T mu / ||T mu||: the slack term |z . x_lo| of the bound is split
                                             // along it (convert.hip sketch_rows_kernel); options.sketch_split = 0: not (A-B switch)
@@ -146,7 +144,6 @@ struct vqa_index {
     int mid_k = 16, mid_pct = 200;          // a second cascade stage of mid_pct % of the first one's tiles for k >= mid_k (options.sketch_mid_k, 0: never; options.sketch_mid_pct)
     int pre_k = 48;                         // a leading quarter of the first stage as a stage of its own for k >= pre_k (options.sketch_pre_k, 0: never)
     int mid_min_tiles = 128;                // ... and for any k on shards of that many tiles per workgroup (options.sketch_mid_min_tiles, 0: by k only)
-    bool cascade = true;                    // options.sketch_cascade = 0: the exact first stage of the narrow sketch form (A-B switch)
     int* sketch_flag_dev_mirror = nullptr;  // device address of the pinned mirror below (mapped host memory: the cascade's last merge writes it)
     int* sketch_flag_host = nullptr;        // pinned mirror of sketch_flag [3], copied once behind the last query tile of a call (read by LATER calls)
     int sketch_cooldown = 0;                // searches left that skip the sketch: data the bound cannot prune would pay the sketch scan
@@ -218,8 +215,7 @@ extern "C" void vqa_index_destroy(vqa_index* ix) {
     }
     if (ix->up_stream) (void)hipStreamDestroy(ix->up_stream);
     for (void* p : {(void*)ix->rows8, (void*)ix->tile_info, ix->q8_stage, (void*)ix->qrow, (void*)ix->qconst,
-                    (void*)ix->regions, (void*)ix->region_cnt, (void*)ix->cand_keys, (void*)ix->cand_cnt, (void*)ix->sketch_flag,
-                    (void*)ix->stage_pos})
+                    (void*)ix->regions, (void*)ix->region_cnt, (void*)ix->cand_keys, (void*)ix->cand_cnt, (void*)ix->sketch_flag})
         if (p) (void)hipFree(p);
     if (ix->rows_rm) (void)hipFree(ix->rows_rm);
     if (ix->mu) (void)hipFree(ix->mu);
@@ -424,8 +420,6 @@ static void dev_env_overlay(vqa_index_options* o) {
     geti("VQA_SEED_DIV", &o->seed_div);
     geti("VQA_STAGE_MIN", &o->stage_min_tiles);
     geti("VQA_STAGE_PCT", &o->stage_pct);
-    geti("VQA_F16_LOOP", &o->f16_loop);
-    geti("VQA_SKETCH_CASCADE", &o->sketch_cascade);
     geti("VQA_SKETCH_ROTATE", &o->sketch_rotate);
     geti("VQA_SKETCH_CENTER", &o->sketch_center);
     geti("VQA_SKETCH_SPLIT", &o->sketch_split);
@@ -473,7 +467,8 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
     VQA_REQUIRE(o.seed_mult >= 1 && o.seed_mult <= 4, "vqa_index_create_ex: seed_mult=%d outside [1, 4]", o.seed_mult);
     VQA_REQUIRE(o.seed_div >= 0, "vqa_index_create_ex: seed_div=%d", o.seed_div);
     VQA_REQUIRE(o.stage_pct >= 1 && o.stage_pct <= 50, "vqa_index_create_ex: stage_pct=%d outside [1, 50]", o.stage_pct);
-    VQA_REQUIRE(o.f16_loop >= 0 && o.f16_loop <= 2, "vqa_index_create_ex: f16_loop=%d", o.f16_loop);
+    VQA_REQUIRE(o.f16_loop == 0, "vqa_index_create_ex: f16_loop=%d: the option is retired (0 only)", o.f16_loop);
+    VQA_REQUIRE(o.sketch_cascade == 1, "vqa_index_create_ex: sketch_cascade=%d: the option is retired (1 only)", o.sketch_cascade);
     VQA_REQUIRE(o.sketch_ring_stages == 5 || o.sketch_ring_stages == 6, "vqa_index_create_ex: sketch_ring_stages=%d (5 or 6)", o.sketch_ring_stages);
     VQA_REQUIRE(o.sketch_mid_pct >= 1 && o.sketch_cooldown >= 0 && o.sketch_mid_k >= 0 && o.sketch_pre_k >= 0 && o.sketch_mid_min_tiles >= 0,
                 "vqa_index_create_ex: a sketch_* option is negative");
@@ -521,7 +516,6 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
     // sketch search: from there on every exact path ends in the re-scoring arithmetic (final_rescore_applies), with or without a sketch
     ix->fin_min_tiles = stage_given ? o.stage_min_tiles : dtype == VQA_F32 ? kPlan.stage_min_f32_sketch : kPlan.stage_min_f16_sketch;
     ix->stage_pct = o.stage_pct;
-    ix->f16_loop = o.f16_loop;
     const int eb = elem_bytes(dtype);
     int rc = VQA_OK;
     do {
@@ -590,7 +584,6 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
                 hipMalloc((void**)&ix->region_cnt, (size_t)ix->max_grid * 4) != hipSuccess ||
                 hipMalloc((void**)&ix->cand_keys, (size_t)VQA_QUERY_TILE * kSketchCap * sizeof(vqa_key)) != hipSuccess ||
                 hipMalloc((void**)&ix->cand_cnt, (size_t)VQA_QUERY_TILE * kSketchSubLists * kSketchCntStride * 4) != hipSuccess || hipMalloc((void**)&ix->sketch_flag, 5 * sizeof(int)) != hipSuccess ||
-                hipMalloc((void**)&ix->stage_pos, (size_t)VQA_QUERY_TILE * max_k * 8) != hipSuccess ||
                 hipHostMalloc((void**)&ix->sketch_flag_host, 5 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
                 hipHostGetDevicePointer((void**)&ix->sketch_flag_dev_mirror, ix->sketch_flag_host, 0) != hipSuccess) {
                 vqa_set_error("vqa_index_create: allocating the int8 sketch (%zu bytes) failed", ix->rows8_bytes);
@@ -602,7 +595,6 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
             // the profitability rule is off there unless asked for)
             if (o.sketch_profit >= 0.f) ix->profit_ratio = o.sketch_profit;
             else ix->profit_ratio = stage_given ? 0.0 : dtype == VQA_F32 ? kPlan.profit_f32 : kPlan.profit_f16;
-            ix->cascade = o.sketch_cascade != 0;
             ix->mid_k = o.sketch_mid_k;
             ix->mid_pct = o.sketch_mid_pct;
             ix->mid_min_tiles = o.sketch_mid_min_tiles;
@@ -680,7 +672,6 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
                 (void)hipMemset(ix->region_cnt, byte, (size_t)ix->max_grid * 4);
                 (void)hipMemset(ix->cand_keys, byte, (size_t)VQA_QUERY_TILE * kSketchCap * sizeof(vqa_key));
                 (void)hipMemset(ix->cand_cnt, byte, (size_t)VQA_QUERY_TILE * kSketchSubLists * kSketchCntStride * 4);
-                (void)hipMemset(ix->stage_pos, byte, (size_t)VQA_QUERY_TILE * max_k2 * 8);
                 if (ix->qoff) (void)hipMemset(ix->qoff, byte, VQA_QUERY_TILE * 4);
                 if (ix->q_rm) (void)hipMemset(ix->q_rm, byte, (size_t)VQA_QUERY_TILE * ix->d_pad * eb);
             }
@@ -843,7 +834,7 @@ static LaunchPlan plan_launch(const vqa_index* ix, int k = 0) {
             // leaves 2.7x fewer (scripts/probes/decomp_probe.py) -- and their number grows with k.  [first | 2 x first | rest].
             // Small k: the level pays for its ~45 us (a launch ramp, a re-scoring, a selection) only on shards of >= 128 tiles per workgroup
             // (10M x 768, k = 10, interleaved A/B: 1.936 -> 1.888 ms; 3M rows: +4 %).
-            if (ix->sketch && ix->cascade && ix->mid_k > 0 && k <= kSketchMaxK &&
+            if (ix->sketch && ix->mid_k > 0 && k <= kSketchMaxK &&
                 (k >= ix->mid_k || (ix->mid_min_tiles > 0 && p.tiles >= (long long)ix->mid_min_tiles * p.grid1))) {
                 const int mid = (int)((long long)p.stage_tiles * ix->mid_pct / 100 / p.grid1) * p.grid1;
                 if (mid > 0 && p.stage_tiles + mid + p.grid1 <= p.tiles) p.mid_tiles = mid;
@@ -943,7 +934,6 @@ static ScoreTopkArgs exact_launch_args(const vqa_index* ix, int nq, int k) {
     a.d_pad = ix->d_pad;
     a.nq = nq;
     a.k = k;
-    a.loop = ix->f16_loop == 1 ? 1 : 0;
     a.partial = ix->partial;
     return a;
 }
@@ -964,12 +954,9 @@ static int seed_pass(vqa_index* ix, const LaunchPlan& p, ScoreTopkArgs a, int ra
                                      thr_out ? thr_out : ix->thr0, 1.0f, rank, 0, nullptr, true, gate, stream, 0, nullptr, 1, tail);
 }
 
-// One sketch scan of tiles [tile_begin, tile_end) against theta = thr[] and the exact scores of what it leaves: per-query
-// constants -> int8 scan -> re-scoring of its candidate pairs (and of `stage_k` first-stage rows per query, ix->stage_pos) into
-// the queries' candidate lists.  `clear`: 1 / 2 = this is the query tile's first scan (counters and overflow flag start at zero;
-// 2: the first tile of the call), 0 = a later one.
-// the merge in front of a sketch scan can write that scan's per-query constants itself (MergeSketchTail: the cascade), which saves the
-// sketch_qconst launch: `thr` == nullptr then
+// The merge in front of a sketch scan writes that scan's per-query constants from the threshold it has just selected (MergeSketchTail),
+// which saves a sketch_qconst launch.  `clear`: 1 / 2 = the next scan is the query tile's first (counters and overflow flag start at
+// zero; 2: the first tile of the call), 0 = a later one.
 static MergeSketchTail qconst_tail(const vqa_index* ix, int clear) {
     MergeSketchTail t;
     t.qconst = ix->qconst;
@@ -990,15 +977,10 @@ static MergeSketchTail qconst_tail(const vqa_index* ix, int clear) {
     return t;
 }
 
-static int sketch_scan_rescore(vqa_index* ix, const LaunchPlan& p, const float* thr, int tile_begin, int tile_end, int nq, int stage_k, int clear,
-                               bool timed, hipStream_t stream) {
-    const int seq = ix->sketch_seq;
+// One sketch scan of tiles [tile_begin, tile_end) against the constants the merge in front of it wrote, and the exact scores of what it
+// leaves: int8 scan -> re-scoring of its candidate pairs into the queries' candidate lists.  `timed`: the scan is bracketed by timing events.
+static int sketch_scan_rescore(vqa_index* ix, const LaunchPlan& p, int tile_begin, int tile_end, int nq, bool timed, hipStream_t stream) {
     int rc = VQA_OK;
-    if (thr)
-        rc = vqa_launch_sketch_qconst(thr, ix->qrow, ix->qrow + VQA_QUERY_TILE, ix->qrow + 2 * VQA_QUERY_TILE, ix->d_pad, ix->qconst,
-                                      ix->cand_cnt, ix->sketch_flag, clear, seq, ix->rotate, ix->center ? ix->qoff : nullptr, 3e-7f * ix->mu_norm, stream,
-                                      ix->wdir ? ix->qrow + 3 * VQA_QUERY_TILE : nullptr, ix->wdir ? ix->qrow + 4 * VQA_QUERY_TILE : nullptr, ix->per_row);
-    if (rc != VQA_OK) return rc;
     SketchScanArgs sk;
     sk.tile_info = reinterpret_cast<const float4*>(ix->tile_info);
     sk.qconst = ix->qconst;
@@ -1027,7 +1009,7 @@ static int sketch_scan_rescore(vqa_index* ix, const LaunchPlan& p, const float* 
     rc = vqa_launch_score_topk(VQA_I8_SKETCH, b, stream);
     if (rc != VQA_OK) return rc;
     if (timed && (rc = timing_event(ix, stream)) != VQA_OK) return rc;
-    return vqa_launch_rescore(ix->regions, ix->region_cnt, kSketchCap, p.grid1, stage_k > 0 ? ix->stage_pos : nullptr, nq, stage_k, ix->rows,
+    return vqa_launch_rescore(ix->regions, ix->region_cnt, kSketchCap, p.grid1, nullptr, nq, 0, ix->rows,
                               ix->rows_rm, ix->q_stage, ix->q_rm, ix->dtype, ix->d_pad, ix->cand_keys, ix->cand_cnt, kSketchCap, ix->sketch_flag, stream);
 }
 
@@ -1169,285 +1151,314 @@ extern "C" int vqa_index_search_host(vqa_index* ix, const void* q_host, int32_t 
     return VQA_OK;
 }
 
-static int search_impl(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B, int32_t k, float* out_scores, int64_t* out_ids,
-                       int64_t* out_pos_or_null, hipStream_t stream) {
-    const int max_k = vqa_score_topk_max_k(ix->dtype);  // per pass over the index
-    const int qeb = q_dtype == VQA_F32 ? 4 : 2;
-    const LaunchPlan p = plan_launch(ix, k);
-    bool sketch_call = false;  // some query tile of this call ran the sketch search
-    bool mirror_by_kernel = false;  // ... and its last merge reports the overflow flags to the host itself (the cascade)
-    // Query tiles of equal size: B = 257 runs as 129 + 128, not 256 + 1 -- the sketch scan's cost follows the waves that hold queries
-    // (32 each: 0.80 ms up to 128 queries, 0.95 at 160, 1.08 at 256 on a 10M-row shard), every other launch of a tile the queries themselves
+// One query tile of a call: queries [q0, q0 + nq) and their rows of the caller's outputs
+struct QueryTile {
+    const void* q = nullptr;  // the tile's first query row
+    int nq = 0;
+    bool first = false, last = false;  // the call's first / last tile
+    float* os = nullptr;
+    int64_t* oi = nullptr;
+    int64_t* op = nullptr;  // or nullptr
+};
+
+// Query tiles of equal size: B = 257 runs as 129 + 128, not 256 + 1 -- the sketch scan's cost follows the waves that hold queries
+// (32 each: 0.80 ms up to 128 queries, 0.95 at 160, 1.08 at 256 on a 10M-row shard), every other launch of a tile the queries themselves.
+// fn(tile) runs for every tile in order; the first error ends the call.
+template <class Fn>
+static int for_each_query_tile(const vqa_index* ix, const void* q, int32_t q_dtype, int32_t B, int32_t k, float* out_scores, int64_t* out_ids,
+                               int64_t* out_pos_or_null, Fn&& fn) {
+    const size_t q_row = (size_t)ix->d * (q_dtype == VQA_F32 ? 4 : 2);
     const int q_tiles = (B + VQA_QUERY_TILE - 1) / VQA_QUERY_TILE;
     const int q_per = q_tiles > 1 ? (B + q_tiles - 1) / q_tiles : VQA_QUERY_TILE;
     for (int q0 = 0; q0 < B; q0 += q_per) {
-        const int nq = B - q0 < q_per ? B - q0 : q_per;
-        float* os = out_scores + (size_t)q0 * k;
-        int64_t* oi = out_ids + (size_t)q0 * k;
-        int64_t* op = out_pos_or_null ? out_pos_or_null + (size_t)q0 * k : nullptr;
-        if (ix->n == 0) {  // empty shard: every slot is padding
-            // reuse the merge kernel on one all-empty partial list, max_k columns at a time
-            VQA_HIP_CHECK(hipMemsetAsync(ix->partial, 0, (size_t)VQA_QUERY_TILE * max_k * sizeof(vqa_key), stream));
-            for (int done = 0; done < k; done += max_k) {
-                const int kk = k - done < max_k ? k - done : max_k;
-                int rc = vqa_launch_merge_partials(ix->partial, 1, max_k, nq, kk, ix->ids, ix->id_base, os, oi, op, nullptr, 1.0f, k,
-                                                   done, nullptr, false, nullptr, stream);
-                if (rc != VQA_OK) return rc;
-            }
-            continue;
+        QueryTile t;
+        t.q = reinterpret_cast<const char*>(q) + (size_t)q0 * q_row;
+        t.nq = B - q0 < q_per ? B - q0 : q_per;
+        t.first = q0 == 0;
+        t.last = q0 + q_per >= B;
+        t.os = out_scores + (size_t)q0 * k;
+        t.oi = out_ids + (size_t)q0 * k;
+        t.op = out_pos_or_null ? out_pos_or_null + (size_t)q0 * k : nullptr;
+        const int rc = fn(t);
+        if (rc != VQA_OK) return rc;
+    }
+    return VQA_OK;
+}
+
+// empty shard: every slot is padding -- the merge kernel on one all-empty partial list, max_k columns at a time
+static int pad_empty_shard(vqa_index* ix, const QueryTile& t, int k, hipStream_t stream) {
+    const int max_k = vqa_score_topk_max_k(ix->dtype);
+    VQA_HIP_CHECK(hipMemsetAsync(ix->partial, 0, (size_t)VQA_QUERY_TILE * max_k * sizeof(vqa_key), stream));
+    for (int done = 0; done < k; done += max_k) {
+        const int kk = k - done < max_k ? k - done : max_k;
+        const int rc = vqa_launch_merge_partials(ix->partial, 1, max_k, t.nq, kk, ix->ids, ix->id_base, t.os, t.oi, t.op, nullptr, 1.0f, k, done,
+                                                 nullptr, false, nullptr, stream);
+        if (rc != VQA_OK) return rc;
+    }
+    return VQA_OK;
+}
+
+// An earlier sketch search of this handle that overflowed into its exact fallback (its flag arrives in the pinned mirror some time after
+// that call; a stale read only delays the reaction by a search) switches the sketch off for a while.  Once per call, before its launches.
+static void update_sketch_pause(vqa_index* ix, int k) {
+    // (the three words arrive by one 12-byte DMA; the number is read first, so a report caught half-way is at worst taken
+    // for the previous call's and looked at again next time)
+    const int seq = __atomic_load_n(ix->sketch_flag_host + 2, __ATOMIC_ACQUIRE);
+    // "over": a candidate buffer overflowed (the call's exact fallback ran), or the call scored so many pairs exactly that the exact
+    // scan would have been cheaper (its result stands: this only decides what the NEXT searches run)
+    const bool over = (__atomic_load_n(ix->sketch_flag_host, __ATOMIC_RELAXED) | __atomic_load_n(ix->sketch_flag_host + 1, __ATOMIC_RELAXED)) != 0 ||
+                      (ix->profit_ratio > 0.0 && (double)pairs_reported(ix) > profit_pairs(ix));
+    if (seq != ix->sketch_seq_seen) {  // a sketch search completed since the last look
+        ix->sketch_seq_seen = seq;
+        // (reports of calls that were already queued when the current pause began say nothing new)
+        const bool fresh = (int)((unsigned)seq - (unsigned)ix->sketch_seq_ignore) > 0;
+        if (over && fresh) {
+            const bool overflowed = (__atomic_load_n(ix->sketch_flag_host, __ATOMIC_RELAXED) | __atomic_load_n(ix->sketch_flag_host + 1, __ATOMIC_RELAXED)) != 0;
+            const int min_k = overflowed ? 0 : (ix->k_of_seq[seq & 63] + 1) / 2;
+            ix->pause_min_k = ix->sketch_cooldown > 0 ? std::min(ix->pause_min_k, min_k) : min_k;
+            ix->sketch_cooldown = ix->sketch_cooldown_cur;
+            // overflow, pause, overflow again: the pause doubles (64, 128, ... 4096 searches)
+            ix->sketch_cooldown_cur = std::min(2 * ix->sketch_cooldown_cur, 64 * ix->sketch_cooldown_len);
+            ix->sketch_seq_ignore = ix->sketch_seq;
+        } else if (!over && fresh && ix->sketch_cooldown == 0) {
+            ix->sketch_cooldown_cur = ix->sketch_cooldown_len;  // a sketch search stood: back to the base pause
         }
-        int rc = VQA_OK;
-        // An earlier sketch search of this handle that overflowed into its exact fallback (its flag arrives in the pinned mirror
-        // some time after that call; a stale read only delays the reaction by a search) switches the sketch off for a while
-        if (ix->sketch && q0 == 0) {
-            // (the three words arrive by one 12-byte DMA; the number is read first, so a report caught half-way is at worst taken
-            // for the previous call's and looked at again next time)
-            const int seq = __atomic_load_n(ix->sketch_flag_host + 2, __ATOMIC_ACQUIRE);
-            // "over": a candidate buffer overflowed (the call's exact fallback ran), or the call scored so many pairs exactly that the exact
-            // scan would have been cheaper (its result stands: this only decides what the NEXT searches run)
-            const bool over = (__atomic_load_n(ix->sketch_flag_host, __ATOMIC_RELAXED) | __atomic_load_n(ix->sketch_flag_host + 1, __ATOMIC_RELAXED)) != 0 ||
-                              (ix->profit_ratio > 0.0 && (double)pairs_reported(ix) > profit_pairs(ix));
-            if (seq != ix->sketch_seq_seen) {  // a sketch search completed since the last look
-                ix->sketch_seq_seen = seq;
-                // (reports of calls that were already queued when the current pause began say nothing new)
-                const bool fresh = (int)((unsigned)seq - (unsigned)ix->sketch_seq_ignore) > 0;
-                if (over && fresh) {
-                    const bool overflowed = (__atomic_load_n(ix->sketch_flag_host, __ATOMIC_RELAXED) | __atomic_load_n(ix->sketch_flag_host + 1, __ATOMIC_RELAXED)) != 0;
-                    const int min_k = overflowed ? 0 : (ix->k_of_seq[seq & 63] + 1) / 2;
-                    ix->pause_min_k = ix->sketch_cooldown > 0 ? std::min(ix->pause_min_k, min_k) : min_k;
-                    ix->sketch_cooldown = ix->sketch_cooldown_cur;
-                    // overflow, pause, overflow again: the pause doubles (64, 128, ... 4096 searches)
-                    ix->sketch_cooldown_cur = std::min(2 * ix->sketch_cooldown_cur, 64 * ix->sketch_cooldown_len);
-                    ix->sketch_seq_ignore = ix->sketch_seq;
-                } else if (!over && fresh && ix->sketch_cooldown == 0) {
-                    ix->sketch_cooldown_cur = ix->sketch_cooldown_len;  // a sketch search stood: back to the base pause
-                }
-            } else if (ix->sketch_cooldown > 0 && k >= ix->pause_min_k) {
-                --ix->sketch_cooldown;  // (the pause counts the searches it applies to)
-            }
-        }
-        const bool any_sketch = sketch_active(ix, p, k) && (ix->sketch_cooldown == 0 || k < ix->pause_min_k);
-        if (any_sketch && q0 == 0) {
-            ++ix->sketch_seq;
-            ix->k_of_seq[ix->sketch_seq & 63] = k;
-            sketch_call = true;
-        }
-        const int sk_clear = q0 == 0 ? 2 : 1;  // the call's first query tile also clears the OR over the tiles
-        const bool use_sketch = any_sketch && k <= max_k && !ix->cascade;  // round 3.s form (options.sketch_cascade = 0: A/B switch)
-        const void* q_tile = reinterpret_cast<const char*>(q) + (size_t)q0 * ix->d * qeb;
-        if (any_sketch) {
-            // one launch: the query tile in the storage type (tiled for the exact kernels, row-major for the re-scoring) and its int8
-            // sketch (every query its own scale) + ||q_lo||, ||q||, q . mu
-            VqaQueryRows qr;
-            qr.rows = q_tile;
-            qr.src_dtype = q_dtype;
-            qr.valid = nq;
-            qr.d = ix->d;
-            qr.scale = ix->scale;
-            qr.stage = ix->q_stage;
-            qr.rowmajor = ix->q_rm;
-            SketchSplit sp;  // + |alpha|, ||z_r||: the query's share of the split slack term
-            sp.wdir = ix->wdir;
-            sp.row_alpha = ix->qrow + 3 * VQA_QUERY_TILE;
-            sp.row_rnorm = ix->qrow + 4 * VQA_QUERY_TILE;
-            sp.per_row = ix->per_row ? 1 : 0;
-            rc = vqa_launch_sketch_rows(nullptr, ix->dtype, 0, VQA_QUERY_TILE, ix->d_pad, ix->d_pad8, nullptr, ix->q8_stage, ix->qrow,
-                                        ix->qrow + VQA_QUERY_TILE, ix->qrow + 2 * VQA_QUERY_TILE, ix->rotate, ix->center ? ix->mu : nullptr,
-                                        false, ix->qoff, stream, &qr, ix->wdir ? &sp : nullptr);
-        } else {
-            rc = vqa_launch_tile_rows(q_tile, q_dtype, 0, VQA_QUERY_TILE, nq, ix->d, ix->d_pad, ix->dtype, ix->scale, ix->q_stage, stream);
+    } else if (ix->sketch_cooldown > 0 && k >= ix->pause_min_k) {
+        --ix->sketch_cooldown;  // (the pause counts the searches it applies to)
+    }
+}
+
+// the query tile -> ix->q_stage in the storage type; with `sketch` in one launch that also writes the row-major copy for the re-scoring
+// and the int8 sketch (every query its own scale) + ||q_lo||, ||q||, q . mu, and |alpha|, ||z_r||: the query's share of the split slack term
+static int stage_query_tile(vqa_index* ix, const QueryTile& t, int32_t q_dtype, bool sketch, hipStream_t stream) {
+    if (!sketch)
+        return vqa_launch_tile_rows(t.q, q_dtype, 0, VQA_QUERY_TILE, t.nq, ix->d, ix->d_pad, ix->dtype, ix->scale, ix->q_stage, stream);
+    VqaQueryRows qr;
+    qr.rows = t.q;
+    qr.src_dtype = q_dtype;
+    qr.valid = t.nq;
+    qr.d = ix->d;
+    qr.scale = ix->scale;
+    qr.stage = ix->q_stage;
+    qr.rowmajor = ix->q_rm;
+    SketchSplit sp;
+    sp.wdir = ix->wdir;
+    sp.row_alpha = ix->qrow + 3 * VQA_QUERY_TILE;
+    sp.row_rnorm = ix->qrow + 4 * VQA_QUERY_TILE;
+    sp.per_row = ix->per_row ? 1 : 0;
+    return vqa_launch_sketch_rows(nullptr, ix->dtype, 0, VQA_QUERY_TILE, ix->d_pad, ix->d_pad8, nullptr, ix->q8_stage, ix->qrow,
+                                  ix->qrow + VQA_QUERY_TILE, ix->qrow + 2 * VQA_QUERY_TILE, ix->rotate, ix->center ? ix->mu : nullptr, false,
+                                  ix->qoff, stream, &qr, ix->wdir ? &sp : nullptr);
+}
+
+// where the rows of a k > 12 search go before the final re-scoring reads them (fin: it re-ranks them in place), or the caller's positions
+static int64_t* wide_positions(vqa_index* ix, bool fin, int k, int64_t* op) {
+    return fin && k > vqa_score_topk_max_k(ix->dtype) ? (op ? op : ix->fin_pos) : op;
+}
+
+// A sketch shard, k <= 128, as a cascade of bounds -- no exact scan of a first stage at all:
+//   exact seeds (2 grid tiles: sub-maxima of real rows)  ->  theta0, a valid lower bound of the k-th best score;
+//   sketch scan of the first stage's tiles against theta0, its candidates scored exactly -> theta1 = the exact k-th best
+//   score of those rows (every row of theirs that reaches theta0 is a candidate; the seeds' k rows are among them);
+//   sketch scan of the other tiles against theta1, candidates scored exactly into the same lists; the k best of a list
+//   are the result.  An overflow anywhere raises sketch_flag, and the exact search runs gated on it: for k <= 12 here, ONE pass
+//   over all tiles seeded with theta0 -- NOT theta1: that is a sum in the re-scoring kernel's order, and the scan's
+//   `score >= threshold` test on MFMA sums could drop the very row that defines it by an ulp; theta0 is an MFMA sum of
+//   the same kernel family (test_small_k_fallback_keeps_the_row_that_defines_theta) --, for larger k the caller's gated exact passes
+//   (theta0 stays in thr_seed for them).  `report`: the call's overflow report to the host, carried by the first gated merge.
+static int cascade_search(vqa_index* ix, const LaunchPlan& p, const QueryTile& t, int k, const MergeSketchTail& report, hipStream_t stream) {
+    const int max_k = vqa_score_topk_max_k(ix->dtype);
+    LaunchPlan pc = p;
+    pc.seed_tiles = std::min(2 * p.grid1, p.stage_tiles);  // (1-4 tiles per workgroup x 6-14 % first stage: 2.00-2.03 ms at 10M rows)
+    pc.grid0 = std::min(pc.seed_tiles, ix->max_grid);
+    pc.seeds_per_tile = 2;
+    ScoreTopkArgs a = exact_launch_args(ix, t.nq, k <= max_k ? k : max_k);
+    // (every merge also does what sits between it and the next scan: the scan's per-query constants from the threshold it
+    // has just selected, the reset of the candidate counters)
+    MergeSketchTail t0 = qconst_tail(ix, t.first ? 2 : 1), t2;  // (the call's first query tile also clears the OR over the tiles)
+    t2.overflow = ix->sketch_flag;
+    t2.min_score = ix->thr0;  // theta1: what the first selection left there
+    int rc = seed_pass(ix, pc, a, k, nullptr, stream, ix->thr_seed, &t0);  // theta0 -> thr_seed
+    if (rc != VQA_OK) return rc;
+    // the stages: [leading quarter of the first (k >= pre_k) |] first | [second (k >= mid_k or a large shard) |] the rest
+    int bounds[4], nb = 0;
+    if (p.pre_tiles > 0) bounds[nb++] = p.pre_tiles;
+    bounds[nb++] = p.stage_tiles;
+    if (p.mid_tiles > 0) bounds[nb++] = p.stage_tiles + p.mid_tiles;
+    bounds[nb++] = p.tiles;
+    for (int l = 0, begin = 0; l < nb; begin = bounds[l], ++l) {
+        const bool last = l == nb - 1;  // (a sketch search times its last scan)
+        if ((rc = sketch_scan_rescore(ix, p, begin, bounds[l], t.nq, last, stream)) != VQA_OK) return rc;
+        if (last) {
+            rc = sketch_select(ix, t.nq, k, t.os, t.oi, t.op, stream, &t2);
+        } else {  // theta_l = the exact k-th best of the rows scanned so far -> thr0 (and the next scan's constants)
+            MergeSketchTail tl = qconst_tail(ix, 0);
+            if (l > 0) tl.min_score = ix->thr0;  // keys below the previous level's threshold cannot matter any more (read while the lists are gathered, before the new threshold is written)
+            rc = sketch_select(ix, t.nq, k, nullptr, nullptr, nullptr, stream, &tl);
         }
         if (rc != VQA_OK) return rc;
-        // k <= 12: one pass.  Larger k, first attempt: ONE pass in which every workgroup keeps its local top 12 above the
-        // seeded threshold (the k-th largest seed, a valid lower bound of the k-th best score), merged to k results.  The
-        // global top-k is inside the union of the local lists unless some workgroup owns more than 12 of them (with 256
-        // workgroups: probability ~1e-10 at k = 256 on unclustered data); vqa_launch_verify_wide checks exactly that on
-        // the device and raises wide_flag.  The exact continuation passes below are then launched GATED on the flag: they
-        // return at once when the one-pass result stands (no host round trip), and overwrite it when it does not.
-        const int* gate = nullptr;
-        // Large fp16 / fp32 shards (the size at which a sketch search can exist for the type): every exact path ends by scoring its rows in
-        // the re-scoring kernel's arithmetic and re-ranking them (sketch.hip final_rescore_kernel), so that the exact scan -- during a
-        // pause of the sketch, behind an overflow, with the sketch off -- returns the bits the sketch path returns.  One pass (k <= 10):
-        // the scan keeps k + 2 rows per query, so rows the MFMA order ranks just below the k-th compete too.
-        const bool fin = final_rescore_applies(ix, p);
-        int64_t* const wide_pos = fin && k > max_k ? (op ? op : ix->fin_pos) : op;  // k > 12: the passes' rows, re-scored in place at the end
-        MergeSketchTail cascade_report;  // (set by the cascade: the report its fallback's first merge carries)
-        if (any_sketch && ix->cascade) {
-            // A sketch shard, k <= 64, as a cascade of bounds -- no exact scan of a first stage at all:
-            //   exact seeds (2 grid tiles: sub-maxima of real rows)  ->  theta0, a valid lower bound of the k-th best score;
-            //   sketch scan of the first stage's tiles against theta0, its candidates scored exactly -> theta1 = the exact k-th best
-            //   score of those rows (every row of theirs that reaches theta0 is a candidate; the seeds' k rows are among them);
-            //   sketch scan of the other tiles against theta1, candidates scored exactly into the same lists; the k best of a list
-            //   are the result.  An overflow anywhere raises sketch_flag, and the exact search runs gated on it: for k <= 12 ONE pass
-            //   over all tiles seeded with theta0 -- NOT theta1: that is a sum in the re-scoring kernel's order, and the scan's
-            //   `score >= threshold` test on MFMA sums could drop the very row that defines it by an ulp; theta0 is an MFMA sum of
-            //   the same kernel family (test_small_k_fallback_keeps_the_row_that_defines_theta) --, for larger k the gated exact
-            //   passes below.
-            LaunchPlan pc = p;
-            pc.seed_tiles = std::min(2 * p.grid1, p.stage_tiles);  // (1-4 tiles per workgroup x 6-14 % first stage: 2.00-2.03 ms at 10M rows)
-            pc.grid0 = std::min(pc.seed_tiles, ix->max_grid);
-            pc.seeds_per_tile = 2;
-            ScoreTopkArgs a = exact_launch_args(ix, nq, k <= max_k ? k : max_k);
-            // (every merge also does what sits between it and the next scan: the scan's per-query constants from the threshold it
-            // has just selected, the reset of the candidate counters; the call's last one reports the overflow flags to the host)
-            MergeSketchTail t0 = qconst_tail(ix, sk_clear), t2;
-            t2.overflow = ix->sketch_flag;
-            t2.min_score = ix->thr0;  // theta1: what the first selection left there
-            // the call's report to the host: written by the gated fallback's merge BEHIND the last selection (any block of that
-            // selection may still raise the overflow flag when block 0 is done: ADVICE r4), by the last query tile of the call
-            MergeSketchTail tm;
-            tm.overflow = ix->sketch_flag;
-            tm.flag_mirror = q0 + q_per >= B ? ix->sketch_flag_dev_mirror : nullptr;
-            tm.mirror_before_gate = 1;
-            cascade_report = tm;
-            rc = seed_pass(ix, pc, a, k, nullptr, stream, ix->thr_seed, &t0);  // theta0 -> thr_seed
+    }
+    if (k > max_k) return VQA_OK;
+    a.thr_init = ix->thr_seed;
+    a.tile_begin = 0;
+    a.tile_end = p.tiles;
+    a.grid = p.grid1;
+    a.gate = ix->sketch_flag;
+    if ((rc = vqa_launch_score_topk(ix->dtype, a, stream)) != VQA_OK) return rc;
+    const bool fin = final_rescore_applies(ix, p);
+    int64_t* fpos = fin ? (t.op ? t.op : ix->fin_pos) : t.op;  // (the final re-scoring reads the rows' positions)
+    rc = vqa_launch_merge_partials(ix->partial, p.grid1, k, t.nq, k, ix->ids, ix->id_base, t.os, t.oi, fpos, nullptr, 1.0f / (ix->scale * ix->scale), k,
+                                   0, nullptr, true, ix->sketch_flag, stream, 0, nullptr, 1, &report);
+    if (rc != VQA_OK) return rc;
+    // the fallback's rows in the sketch path's arithmetic (gated like the fallback itself)
+    if (fin)
+        rc = vqa_launch_final_rescore(fpos, k, t.nq, k, k, ix->rows, nullptr, ix->q_stage, nullptr, ix->dtype, ix->d_pad, ix->ids, ix->id_base,
+                                      t.os, t.oi, t.op, k, ix->sketch_flag, stream);
+    return rc;
+}
+
+// Larger k without a sketch, first attempt: ONE pass in which every workgroup keeps its local top 12 above the seeded threshold (the
+// k-th largest seed, a valid lower bound of the k-th best score), merged to k results.  The global top-k is inside the union of the
+// local lists unless some workgroup owns more than 12 of them (with 256 workgroups: probability ~1e-10 at k = 256 on unclustered data);
+// vqa_launch_verify_wide checks exactly that on the device and raises wide_flag.  The exact continuation passes behind it are launched
+// GATED on the flag: they return at once when the one-pass result stands (no host round trip), and overwrite it when it does not.
+static bool wide_attempt_applies(const vqa_index* ix, const LaunchPlan& p, int k) {
+    return k > vqa_score_topk_max_k(ix->dtype) && ix->wide && k <= 3 * p.grid1 && p.seed_tiles > 0;
+}
+
+static int wide_attempt(vqa_index* ix, const LaunchPlan& p, const QueryTile& t, int k, hipStream_t stream) {
+    const int max_k = vqa_score_topk_max_k(ix->dtype);
+    ScoreTopkArgs a = exact_launch_args(ix, t.nq, max_k);
+    VQA_HIP_CHECK(hipMemsetAsync(ix->wide_flag, 0, sizeof(int), stream));
+    int rc = seed_pass(ix, p, a, k, nullptr, stream);
+    if (rc != VQA_OK) return rc;
+    a.thr_init = ix->thr0;
+    a.tile_begin = 0;
+    a.tile_end = p.tiles;
+    a.grid = p.grid1;
+    if ((rc = vqa_launch_score_topk(ix->dtype, a, stream)) != VQA_OK) return rc;
+    rc = vqa_launch_merge_partials(ix->partial, p.grid1, max_k, t.nq, k, ix->ids, ix->id_base, t.os, t.oi,
+                                   wide_positions(ix, final_rescore_applies(ix, p), k, t.op), nullptr, 1.0f / (ix->scale * ix->scale), k, 0,
+                                   ix->upper, true, nullptr, stream);
+    if (rc != VQA_OK) return rc;
+    return vqa_launch_verify_wide(ix->partial, p.grid1, max_k, t.nq, ix->upper, ix->wide_flag, stream);
+}
+
+// How exact_passes() runs: where its passes' starting threshold comes from, what gates them, and the scan's form
+struct ExactPasses {
+    enum Threshold {
+        kNone,      // -inf (the filtered scan; a plan without a seed pass)
+        kOwnSeed,   // every pass runs its own seed pass -> thr0
+        kThr0,      // the k-th largest seed the wide attempt left in thr0 (nothing overwrites it)
+        kThrSeed,   // the cascade's theta0 in thr_seed: it bounds the k-th best score from below and with it every pass's 12 j-th
+    } thr = kNone;
+    const int* gate = nullptr;   // the passes run only when the flag is up (wide_flag, sketch_flag), or nullptr
+    bool staged = false;         // one pass of a large shard as a first stage + the main launch (k <= 12)
+    const FilterScanArgs* filter = nullptr;  // MODE 3 over the listed tiles, or nullptr
+    const MergeSketchTail* report = nullptr;  // carried by the first pass's merge (behind a cascade: the call's overflow report)
+};
+
+// Exact passes: k <= 12 needs one; larger k ceil(k / 12), each admitting only keys strictly below the last key already returned (keys are
+// distinct, so the continuation is exact); every pass is a full scan of the shard.  Large fp16 / fp32 shards (the size at which a sketch
+// search can exist for the type): the rows end in the re-scoring kernel's arithmetic and are re-ranked (sketch.hip final_rescore_kernel),
+// so that the exact scan -- during a pause of the sketch, behind an overflow, with the sketch off -- returns the bits the sketch path
+// returns.  One pass (k <= 10): the scan keeps k + 2 rows per query, so rows the MFMA order ranks just below the k-th compete too.
+static int exact_passes(vqa_index* ix, const LaunchPlan& p, const QueryTile& t, int k, const ExactPasses& x, hipStream_t stream) {
+    const int max_k = vqa_score_topk_max_k(ix->dtype);
+    const bool fin = final_rescore_applies(ix, p);
+    const bool one_pass_fin = fin && k <= max_k;  // its k + kx rows go to the scratch arrays, the re-scoring writes the caller's
+    const int kx = fin && k + 2 <= max_k && ix->n >= k + 2 ? 2 : 0;  // margin rows of a one-pass exact search
+    int64_t* const wide_pos = wide_positions(ix, fin, k, t.op);  // k > 12: the passes' rows, re-scored in place at the end
+    const bool sketch_gated = x.gate && x.gate == ix->sketch_flag;  // the sketch's fallback: a sketch search times its sketch scan instead
+    const bool timed = ix->timing && !sketch_gated;
+    const float* thr = x.thr == ExactPasses::kNone ? nullptr : x.thr == ExactPasses::kThrSeed ? ix->thr_seed : ix->thr0;
+    const int lists = x.staged ? 2 * p.grid1 : p.grid1;
+    int rc = VQA_OK;
+    for (int done = 0; done < k; done += max_k) {
+        const int kk = (k - done < max_k ? k - done : max_k) + kx;
+        ScoreTopkArgs a = exact_launch_args(ix, t.nq, kk);
+        a.upper = done > 0 ? ix->upper : nullptr;
+        a.gate = x.gate;
+        if (x.thr == ExactPasses::kOwnSeed && (rc = seed_pass(ix, p, a, kk, x.gate, stream)) != VQA_OK) return rc;
+        a.thr_init = thr;
+        a.tile_begin = 0;
+        a.tile_end = p.tiles;
+        a.grid = p.grid1;
+        a.filter = x.filter;
+        if (x.staged) {
+            // first stage: tiles [0, stage_tiles) with the seeds' thresholds -> lists [0, grid) of every query's row of 2 grid
+            // lists; their merge (thresholds only) = the exact k-th best score of those rows, seeds the main launch
+            a.row_lists = lists;
+            a.list_offset = 0;
+            a.tile_end = p.stage_tiles;
+            a.first_stage = true;
+            if ((rc = vqa_launch_score_topk(ix->dtype, a, stream)) != VQA_OK) return rc;
+            rc = vqa_launch_merge_partials(ix->partial, p.grid1, kk, t.nq, kk, nullptr, 0, nullptr, nullptr, nullptr, ix->thr0, 1.0f, kk, 0, nullptr,
+                                           true, x.gate, stream, lists);
             if (rc != VQA_OK) return rc;
-            // the stages: [leading quarter of the first (k >= pre_k) |] first | [second (k >= mid_k or a large shard) |] the rest
-            int bounds[4], nb = 0;
-            if (p.pre_tiles > 0) bounds[nb++] = p.pre_tiles;
-            bounds[nb++] = p.stage_tiles;
-            if (p.mid_tiles > 0) bounds[nb++] = p.stage_tiles + p.mid_tiles;
-            bounds[nb++] = p.tiles;
-            for (int l = 0, begin = 0; l < nb; begin = bounds[l], ++l) {
-                const bool last = l == nb - 1;
-                rc = sketch_scan_rescore(ix, p, nullptr, begin, bounds[l], nq, 0, l == 0 ? sk_clear : 0, last, stream);
-                if (rc != VQA_OK) return rc;
-                if (last) {
-                    rc = sketch_select(ix, nq, k, os, oi, op, stream, &t2);
-                } else {  // theta_l = the exact k-th best of the rows scanned so far -> thr0 (and the next scan's constants)
-                    MergeSketchTail tl = qconst_tail(ix, 0);
-                    if (l > 0) tl.min_score = ix->thr0;  // keys below the previous level's threshold cannot matter any more (read while the lists are gathered, before the new threshold is written)
-                    rc = sketch_select(ix, nq, k, nullptr, nullptr, nullptr, stream, &tl);
-                }
-                if (rc != VQA_OK) return rc;
-            }
-            mirror_by_kernel = true;
-            if (k <= max_k) {
-                a.thr_init = ix->thr_seed;
-                a.tile_begin = 0;
-                a.tile_end = p.tiles;
-                a.grid = p.grid1;
-                a.gate = ix->sketch_flag;
-                rc = vqa_launch_score_topk(ix->dtype, a, stream);
-                if (rc != VQA_OK) return rc;
-                int64_t* fpos = fin ? (op ? op : ix->fin_pos) : op;  // (the final re-scoring reads the rows' positions)
-                rc = vqa_launch_merge_partials(ix->partial, p.grid1, k, nq, k, ix->ids, ix->id_base, os, oi, fpos, nullptr,
-                                               1.0f / (ix->scale * ix->scale), k, 0, nullptr, true, ix->sketch_flag, stream, 0, nullptr, 1,
-                                               &cascade_report);
-                if (rc != VQA_OK) return rc;
-                // the fallback's rows in the sketch path's arithmetic (gated like the fallback itself)
-                if (fin && (rc = vqa_launch_final_rescore(fpos, k, nq, k, k, ix->rows, nullptr, ix->q_stage, nullptr, ix->dtype, ix->d_pad, ix->ids,
-                                                          ix->id_base, os, oi, op, k, ix->sketch_flag, stream)) != VQA_OK)
-                    return rc;
-                continue;
-            }
-            gate = ix->sketch_flag;  // larger k: the gated exact passes below
-        } else if (k > max_k && ix->wide && k <= 3 * p.grid1 && p.seed_tiles > 0) {
-            ScoreTopkArgs a = exact_launch_args(ix, nq, max_k);
-            VQA_HIP_CHECK(hipMemsetAsync(ix->wide_flag, 0, sizeof(int), stream));
-            rc = seed_pass(ix, p, a, k, nullptr, stream);
-            if (rc != VQA_OK) return rc;
-            a.thr_init = ix->thr0;
-            a.tile_begin = 0;
+            a.first_stage = false;
+            a.tile_begin = p.stage_tiles;
             a.tile_end = p.tiles;
-            a.grid = p.grid1;
-            a.seed_only = false;
-            rc = vqa_launch_score_topk(ix->dtype, a, stream);
-            if (rc != VQA_OK) return rc;
-            rc = vqa_launch_merge_partials(ix->partial, p.grid1, max_k, nq, k, ix->ids, ix->id_base, os, oi, wide_pos, nullptr,
-                                           1.0f / (ix->scale * ix->scale), k, 0, ix->upper, true, nullptr, stream);
-            if (rc != VQA_OK) return rc;
-            rc = vqa_launch_verify_wide(ix->partial, p.grid1, max_k, nq, ix->upper, ix->wide_flag, stream);
-            if (rc != VQA_OK) return rc;
-            gate = ix->wide_flag;
+            a.list_offset = p.grid1;
         }
-        // Exact passes: k <= 12 needs one; larger k ceil(k / 12), each admitting only keys strictly below the last key already
-        // returned (keys are distinct, so the continuation is exact); every pass is a full scan of the shard.
-        const int kx = fin && k + 2 <= max_k && !use_sketch && ix->n >= k + 2 ? 2 : 0;  // margin rows of a one-pass exact search
-        for (int done = 0; done < k; done += max_k) {
-            const int kk = (k - done < max_k ? k - done : max_k) + kx;
-            const vqa_key* upper = done > 0 ? ix->upper : nullptr;
-            ScoreTopkArgs a = exact_launch_args(ix, nq, kk);
-            a.upper = upper;
-            a.gate = gate;
-            // The gated exact passes behind a cascade (k > 12: ceil(k / 12) of them, each "returns at once" -- but an empty launch still costs
-            // its ~5 us of dispatch: four launches per pass were 200 us of a 3 ms search at k = 100) need no seed pass of their own: theta0,
-            // the k-th largest exact seed of the cascade, bounds the k-th best score from below and with it every pass's 12 j-th.
-            // The same holds behind the one-pass attempt of a shard without a sketch (gate = wide_flag): its seed pass left the k-th
-            // largest seed in thr0, and nothing overwrites it when the continuation passes do not seed themselves.
-            const bool cascade_fallback = any_sketch && ix->cascade && gate == ix->sketch_flag;
-            const bool wide_fallback = gate != nullptr && gate == ix->wide_flag && p.grid0 > 0;
-            if (!cascade_fallback && !wide_fallback && p.grid0 > 0 && (rc = seed_pass(ix, p, a, kk, gate, stream)) != VQA_OK) return rc;
-            a.thr_init = cascade_fallback ? ix->thr_seed : p.grid0 > 0 ? ix->thr0 : nullptr;
-            a.tile_begin = 0;
-            a.tile_end = p.tiles;
-            a.grid = p.grid1;
-            a.seed_only = false;
-            const bool staged = p.stage_tiles > 0 && k <= max_k && p.grid0 > 0;  // one exact pass of a large shard
-            int lists = p.grid1;
-            if (staged) {
-                // first stage: tiles [0, stage_tiles) with the seeds' thresholds -> lists [0, grid) of every query's row of 2 grid
-                // lists; their merge (thresholds only) = the exact k-th best score of those rows, seeds the main launch
-                lists = 2 * p.grid1;
-                a.row_lists = lists;
-                a.list_offset = 0;
-                a.tile_end = p.stage_tiles;
-                a.first_stage = true;
-                rc = vqa_launch_score_topk(ix->dtype, a, stream);
-                if (rc != VQA_OK) return rc;
-                rc = vqa_launch_merge_partials(ix->partial, p.grid1, kk, nq, kk, nullptr, 0, nullptr, nullptr,
-                                               use_sketch ? reinterpret_cast<int64_t*>(ix->stage_pos) : nullptr, ix->thr0, 1.0f, kk, 0,
-                                               nullptr, true, gate, stream, lists);
-                if (rc != VQA_OK) return rc;
-                a.first_stage = false;
-                a.tile_begin = p.stage_tiles;
-                a.tile_end = p.tiles;
-                a.list_offset = p.grid1;
-                if (ix->f16_loop == 2) a.loop = 1;
-                if (use_sketch) {
-                    // Main launch over the int8 sketch (half the bytes, twice the MFMA rate per row): with theta = the first stage's
-                    // exact k-th best score it leaves the (query, row) pairs whose rigorous upper bound reaches theta; those and the
-                    // first stage's k rows are scored exactly and the k best of each query's list are the result.  Should a
-                    // candidate buffer fill up (adversarial data: the bound prunes nothing), sketch_flag sends the search through
-                    // the exact main launch below, gated on the flag.
-                    rc = sketch_scan_rescore(ix, p, ix->thr0, p.stage_tiles, p.tiles, nq, kk, sk_clear, true, stream);
-                    if (rc != VQA_OK) return rc;
-                    MergeSketchTail tf;
-                    tf.overflow = ix->sketch_flag;  // (a list longer than the selection's LDS raises it)
-                    rc = sketch_select(ix, nq, kk, os, oi, op, stream, &tf);
-                    if (rc != VQA_OK) return rc;
-                    a.gate = ix->sketch_flag;  // the exact main launch + merge below: only when the flag is up
-                }
-            }
-            const bool time_it = ix->timing && !(staged && use_sketch) && !(gate && gate == ix->sketch_flag);  // a sketch search times its sketch scan instead
-            if (time_it && (rc = timing_event(ix, stream)) != VQA_OK) return rc;
-            rc = vqa_launch_score_topk(ix->dtype, a, stream);
-            if (rc != VQA_OK) return rc;
-            if (time_it && (rc = timing_event(ix, stream)) != VQA_OK) return rc;
-            const bool report_here = cascade_fallback && done == 0;  // (k > 12 behind a cascade: the first gated pass's merge reports)
-            const bool one_pass_fin = fin && k <= max_k && !use_sketch;  // its k + kx rows go to the scratch arrays, the re-scoring writes the caller's
-            rc = vqa_launch_merge_partials(ix->partial, lists, kk, nq, kk, ix->ids, ix->id_base, one_pass_fin ? ix->fin_scores : os,
-                                           one_pass_fin ? ix->fin_ids : oi, one_pass_fin ? ix->fin_pos : wide_pos, nullptr,
-                                           1.0f / (ix->scale * ix->scale), one_pass_fin ? kk : k, done, done + kk < k ? ix->upper : nullptr, true,
-                                           staged && use_sketch ? ix->sketch_flag : gate, stream, 0, nullptr, 1,
-                                           report_here ? &cascade_report : nullptr);
-            if (rc != VQA_OK) return rc;
-            if (one_pass_fin && (rc = vqa_launch_final_rescore(ix->fin_pos, kk, nq, kk, k, ix->rows, nullptr, ix->q_stage, nullptr, ix->dtype, ix->d_pad,
-                                                               ix->ids, ix->id_base, os, oi, op, k, gate, stream)) != VQA_OK)
-                return rc;
-        }
-        // k > 12: the passes' k rows (the verified one-pass attempt's, or the gated continuation passes') re-scored and re-ranked in place;
-        // behind a cascade the passes only ran if its flag is up, and so does this
-        if (fin && k > max_k && !use_sketch &&
-            (rc = vqa_launch_final_rescore(wide_pos, k, nq, k, k, ix->rows, nullptr, ix->q_stage, nullptr, ix->dtype, ix->d_pad, ix->ids, ix->id_base,
-                                           os, oi, op, k, gate == ix->sketch_flag ? gate : nullptr, stream)) != VQA_OK)
+        if (timed && (rc = timing_event(ix, stream)) != VQA_OK) return rc;
+        if ((rc = vqa_launch_score_topk(ix->dtype, a, stream)) != VQA_OK) return rc;
+        if (timed && (rc = timing_event(ix, stream)) != VQA_OK) return rc;
+        rc = vqa_launch_merge_partials(ix->partial, lists, kk, t.nq, kk, ix->ids, ix->id_base, one_pass_fin ? ix->fin_scores : t.os,
+                                       one_pass_fin ? ix->fin_ids : t.oi, one_pass_fin ? ix->fin_pos : wide_pos, nullptr,
+                                       1.0f / (ix->scale * ix->scale), one_pass_fin ? kk : k, done, done + kk < k ? ix->upper : nullptr, true,
+                                       x.gate, stream, 0, nullptr, 1, done == 0 ? x.report : nullptr);
+        if (rc != VQA_OK) return rc;
+        if (one_pass_fin && (rc = vqa_launch_final_rescore(ix->fin_pos, kk, t.nq, kk, k, ix->rows, nullptr, ix->q_stage, nullptr, ix->dtype, ix->d_pad,
+                                                           ix->ids, ix->id_base, t.os, t.oi, t.op, k, x.gate, stream)) != VQA_OK)
             return rc;
     }
-    // the overflow flags of this call (its last tile's, the OR over the earlier ones, the call's number) -> the pinned mirror a later
-    // call's cool-down bookkeeping reads
-    if (sketch_call && !mirror_by_kernel)
-        VQA_HIP_CHECK(hipMemcpyAsync(ix->sketch_flag_host, ix->sketch_flag, 5 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    return VQA_OK;
+    // k > 12: the passes' k rows (the verified one-pass attempt's, or the gated continuation passes') re-scored and re-ranked in place;
+    // behind a cascade the passes only ran if its flag is up, and so does this
+    if (fin && k > max_k)
+        rc = vqa_launch_final_rescore(wide_pos, k, t.nq, k, k, ix->rows, nullptr, ix->q_stage, nullptr, ix->dtype, ix->d_pad, ix->ids, ix->id_base,
+                                      t.os, t.oi, t.op, k, sketch_gated ? x.gate : nullptr, stream);
+    return rc;
+}
+
+// The plan of an unfiltered search, per query tile: stage the queries -> the sketch cascade | the verified wide attempt | nothing ->
+// the exact passes (behind the first two: gated on their flag).  The sketch's pause state is updated once per call, before any launch.
+static int search_impl(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B, int32_t k, float* out_scores, int64_t* out_ids,
+                       int64_t* out_pos_or_null, hipStream_t stream) {
+    const int max_k = vqa_score_topk_max_k(ix->dtype);  // per pass over the index
+    const LaunchPlan p = plan_launch(ix, k);
+    if (ix->sketch) update_sketch_pause(ix, k);
+    const bool sketch = sketch_active(ix, p, k) && (ix->sketch_cooldown == 0 || k < ix->pause_min_k);
+    if (sketch) {
+        ++ix->sketch_seq;
+        ix->k_of_seq[ix->sketch_seq & 63] = k;
+    }
+    return for_each_query_tile(ix, q, q_dtype, B, k, out_scores, out_ids, out_pos_or_null, [&](const QueryTile& t) {
+        if (ix->n == 0) return pad_empty_shard(ix, t, k, stream);
+        int rc = stage_query_tile(ix, t, q_dtype, sketch, stream);
+        if (rc != VQA_OK) return rc;
+        ExactPasses x;
+        MergeSketchTail report;
+        if (sketch) {
+            // the call's report to the host: written by the gated fallback's first merge BEHIND the last selection (any block of that
+            // selection may still raise the overflow flag when block 0 is done: ADVICE r4), by the last query tile of the call
+            report.overflow = ix->sketch_flag;
+            report.flag_mirror = t.last ? ix->sketch_flag_dev_mirror : nullptr;
+            report.mirror_before_gate = 1;
+            if ((rc = cascade_search(ix, p, t, k, report, stream)) != VQA_OK || k <= max_k) return rc;
+            x.thr = ExactPasses::kThrSeed;
+            x.gate = ix->sketch_flag;
+            x.report = &report;
+        } else if (wide_attempt_applies(ix, p, k)) {
+            if ((rc = wide_attempt(ix, p, t, k, stream)) != VQA_OK) return rc;
+            x.thr = ExactPasses::kThr0;
+            x.gate = ix->wide_flag;
+        } else {
+            x.thr = p.grid0 > 0 ? ExactPasses::kOwnSeed : ExactPasses::kNone;
+            x.staged = p.stage_tiles > 0 && k <= max_k && p.grid0 > 0;
+        }
+        return exact_passes(ix, p, t, k, x, stream);
+    });
 }
 
 // ---- filtered search: the exact top-k among the rows whose bit is set in a device bitmap (vqa_index_search_filtered).
@@ -1459,12 +1470,9 @@ static int search_impl(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B,
 // same way, so an all-ones bitmap returns the bits of vqa_index_search on the handle.
 static int filtered_impl(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B, int32_t k, const uint32_t* allow, float* out_scores,
                          int64_t* out_ids, int64_t* out_pos_or_null, hipStream_t stream) {
-    const int max_k = vqa_score_topk_max_k(ix->dtype);
-    const int qeb = q_dtype == VQA_F32 ? 4 : 2;
     const LaunchPlan p = plan_launch(ix, k);
-    const int tiles = (int)((ix->n + 255) / 256);
     int* const list = ix->flt_tiles;
-    int* const count = ix->flt_tiles + tiles;
+    int* const count = ix->flt_tiles + p.tiles;
     int rc = VQA_OK;
     if (ix->n > 0 && (rc = vqa_launch_filter_tiles(allow, ix->n, list, count, count + 1, stream)) != VQA_OK) return rc;
     FilterScanArgs f;
@@ -1472,55 +1480,13 @@ static int filtered_impl(vqa_index* ix, const void* q, int32_t q_dtype, int32_t 
     f.count = count;
     f.allow = allow;
     f.nwords = (ix->n + 31) / 32;
-    const bool fin = final_rescore_applies(ix, p);
-    const int q_tiles = (B + VQA_QUERY_TILE - 1) / VQA_QUERY_TILE;
-    const int q_per = q_tiles > 1 ? (B + q_tiles - 1) / q_tiles : VQA_QUERY_TILE;
-    for (int q0 = 0; q0 < B; q0 += q_per) {
-        const int nq = B - q0 < q_per ? B - q0 : q_per;
-        float* os = out_scores + (size_t)q0 * k;
-        int64_t* oi = out_ids + (size_t)q0 * k;
-        int64_t* op = out_pos_or_null ? out_pos_or_null + (size_t)q0 * k : nullptr;
-        if (ix->n == 0) {  // empty shard: every slot is padding (as vqa_index_search)
-            VQA_HIP_CHECK(hipMemsetAsync(ix->partial, 0, (size_t)VQA_QUERY_TILE * max_k * sizeof(vqa_key), stream));
-            for (int done = 0; done < k; done += max_k) {
-                const int kk = k - done < max_k ? k - done : max_k;
-                if ((rc = vqa_launch_merge_partials(ix->partial, 1, max_k, nq, kk, ix->ids, ix->id_base, os, oi, op, nullptr, 1.0f, k, done, nullptr,
-                                                    false, nullptr, stream)) != VQA_OK)
-                    return rc;
-            }
-            continue;
-        }
-        const void* q_tile = reinterpret_cast<const char*>(q) + (size_t)q0 * ix->d * qeb;
-        if ((rc = vqa_launch_tile_rows(q_tile, q_dtype, 0, VQA_QUERY_TILE, nq, ix->d, ix->d_pad, ix->dtype, ix->scale, ix->q_stage, stream)) != VQA_OK)
-            return rc;
-        // as search_impl's exact passes: k + 2 rows of one pass, or the k rows of the continuation passes, re-scored at the end where fin
-        const int kx = fin && k + 2 <= max_k && ix->n >= k + 2 ? 2 : 0;
-        int64_t* const wide_pos = fin && k > max_k ? (op ? op : ix->fin_pos) : op;
-        const bool one_pass_fin = fin && k <= max_k;
-        for (int done = 0; done < k; done += max_k) {
-            const int kk = (k - done < max_k ? k - done : max_k) + kx;
-            ScoreTopkArgs a = exact_launch_args(ix, nq, kk);
-            a.upper = done > 0 ? ix->upper : nullptr;
-            a.grid = p.grid1;
-            a.filter = &f;
-            if (ix->timing && (rc = timing_event(ix, stream)) != VQA_OK) return rc;
-            if ((rc = vqa_launch_score_topk(ix->dtype, a, stream)) != VQA_OK) return rc;
-            if (ix->timing && (rc = timing_event(ix, stream)) != VQA_OK) return rc;
-            rc = vqa_launch_merge_partials(ix->partial, p.grid1, kk, nq, kk, ix->ids, ix->id_base, one_pass_fin ? ix->fin_scores : os,
-                                           one_pass_fin ? ix->fin_ids : oi, one_pass_fin ? ix->fin_pos : wide_pos, nullptr,
-                                           1.0f / (ix->scale * ix->scale), one_pass_fin ? kk : k, done, done + kk < k ? ix->upper : nullptr, true,
-                                           nullptr, stream);
-            if (rc != VQA_OK) return rc;
-            if (one_pass_fin && (rc = vqa_launch_final_rescore(ix->fin_pos, kk, nq, kk, k, ix->rows, nullptr, ix->q_stage, nullptr, ix->dtype, ix->d_pad,
-                                                               ix->ids, ix->id_base, os, oi, op, k, nullptr, stream)) != VQA_OK)
-                return rc;
-        }
-        if (fin && k > max_k &&
-            (rc = vqa_launch_final_rescore(wide_pos, k, nq, k, k, ix->rows, nullptr, ix->q_stage, nullptr, ix->dtype, ix->d_pad, ix->ids, ix->id_base,
-                                           os, oi, op, k, nullptr, stream)) != VQA_OK)
-            return rc;
-    }
-    return VQA_OK;
+    ExactPasses x;  // no seed pass, one stage
+    x.filter = &f;
+    return for_each_query_tile(ix, q, q_dtype, B, k, out_scores, out_ids, out_pos_or_null, [&](const QueryTile& t) {
+        if (ix->n == 0) return pad_empty_shard(ix, t, k, stream);
+        if ((rc = stage_query_tile(ix, t, q_dtype, false, stream)) != VQA_OK) return rc;
+        return exact_passes(ix, p, t, k, x, stream);
+    });
 }
 
 extern "C" int vqa_index_search_filtered(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B, int32_t k, const uint32_t* allow_bits,

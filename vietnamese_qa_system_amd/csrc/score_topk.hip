@@ -111,33 +111,6 @@ __device__ __forceinline__ void mma_block_mx(f32x4 (&acc)[8][4], const v8i (&a)[
                                                                            kUnitScale);
 }
 
-// fp16 on the same K-step-pair operands (the stagger loop, LOOP = 1): the low / high 16 bytes of a lane's 32-byte operand are
-// its fragments of the even / odd K-step; 2 x 32 v_mfma_f32_16x16x32_f16, K-step outermost (consecutive MFMAs hit different
-// accumulators)
-typedef int v4i __attribute__((ext_vector_type(4)));
-template <int DT>
-__device__ __forceinline__ void mma_pair(f32x4 (&acc)[8][4], const v8i (&a)[8], const v8i (&b)[4]) {
-    if constexpr (DT == VQA_FP8_E4M3) {
-        mma_block_mx<0, 8>(acc, a, b);
-    } else {
-        static_assert(DT == VQA_F16, "K-step pairs: fp8 (block-scaled MFMA) or fp16");
-#pragma unroll
-        for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-                acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                    __builtin_bit_cast(half8, __builtin_shufflevector(a[mi], a[mi], 0, 1, 2, 3)),
-                    __builtin_bit_cast(half8, __builtin_shufflevector(b[ni], b[ni], 0, 1, 2, 3)), acc[mi][ni], 0, 0, 0);
-#pragma unroll
-        for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-                acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                    __builtin_bit_cast(half8, __builtin_shufflevector(a[mi], a[mi], 4, 5, 6, 7)),
-                    __builtin_bit_cast(half8, __builtin_shufflevector(b[ni], b[ni], 4, 5, 6, 7)), acc[mi][ni], 0, 0, 0);
-    }
-}
-
 // row groups [M0, M1) x all four query groups; sub-step outermost so consecutive MFMAs hit different accumulators
 // (v_mfma_f32_16x16x4_f32 has a 40-cycle dependent latency against a 32-cycle issue)
 template <int DT, int T, int M0, int M1>
@@ -435,7 +408,7 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // fp16 / fp32: group = corpus-row half (the two groups run the K-step memory-first / matrix-first).
     // fp8: group = QUERY half (the two groups run one slot apart and own disjoint candidate lists, see stagger_loop).
-    constexpr bool kStagger = DT == VQA_FP8_E4M3 || (DT == VQA_F16 && LOOP == 1);  // LOOP 1: fp16 on the K-step-pair stagger loop
+    constexpr bool kStagger = DT == VQA_FP8_E4M3;
     const int grp = wave >> 2;                              // waves w and w + 4 share a SIMD: one of each group
     const int wm = kStagger ? (wave >> 1) & 1 : grp;        // corpus-row half
     const int wn = kStagger ? 2 * grp + (wave & 1) : wave & 3;  // query quarter
@@ -1315,7 +1288,7 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
                              "+v"(a2[7]));
                 VQA_SB();
 #if !(VQA_ABLATE & 4)
-                mma_pair<DT>(acc, a2, b2);
+                mma_block_mx<0, 8>(acc, a2, b2);
 #endif
 #pragma unroll
                 for (int mi = 0; mi < 8; ++mi)
@@ -1399,21 +1372,21 @@ int vqa_score_topk_max_k(int dtype) {
 
 int vqa_score_topk_seeds_per_tile() { return kSeedsPerTile; }
 
-template <int DT, int LOOP>
+template <int DT>
 static int launch_dt(const ScoreTopkArgs& a, int KT, int lds, hipStream_t stream) {
     static VqaPerDeviceOnce once;
     int rc = once.run([&](int) -> int {
-        VQA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(score_topk_kernel<0, DT, 0, LOOP>),
+        VQA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(score_topk_kernel<0, DT, 0, 0>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        VQA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(score_topk_kernel<1, DT, 0, LOOP>),
+        VQA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(score_topk_kernel<1, DT, 0, 0>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        VQA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(score_topk_kernel<1, DT, 1, LOOP>),
+        VQA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(score_topk_kernel<1, DT, 1, 0>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         return VQA_OK;
     });
     if (rc != VQA_OK) return rc;
-    auto kern = a.seed_only ? score_topk_kernel<0, DT, 0, LOOP>
-                            : a.first_stage ? score_topk_kernel<1, DT, 1, LOOP> : score_topk_kernel<1, DT, 0, LOOP>;
+    auto kern = a.seed_only ? score_topk_kernel<0, DT, 0, 0>
+                            : a.first_stage ? score_topk_kernel<1, DT, 1, 0> : score_topk_kernel<1, DT, 0, 0>;
     hipLaunchKernelGGL(kern, dim3(a.grid), dim3(kThreads), lds, stream, a.x, a.q, a.thr_init, a.upper, a.partial, (long long)a.n,
                        KT, a.nq, a.k, a.tile_begin, a.tile_end, a.gate, a.row_lists > 0 ? a.row_lists : a.grid, a.list_offset,
                        a.seeds_per_tile, SketchScanArgs{});
@@ -1510,9 +1483,9 @@ int vqa_launch_score_topk(int dtype, const ScoreTopkArgs& a, hipStream_t stream)
                 a.tile_end - a.tile_begin);
     const int lds = vqa_score_topk_lds_bytes(dtype, a.k);
     const int KT = a.d_pad * esize / kRowBytes;  // even
-    if (dtype == VQA_F16) return a.loop == 1 ? launch_dt<VQA_F16, 1>(a, KT, lds, stream) : launch_dt<VQA_F16, 0>(a, KT, lds, stream);
-    if (dtype == VQA_FP8_E4M3) return launch_dt<VQA_FP8_E4M3, 0>(a, KT, lds, stream);
-    return launch_dt<VQA_F32, 0>(a, KT, lds, stream);
+    if (dtype == VQA_F16) return launch_dt<VQA_F16>(a, KT, lds, stream);
+    if (dtype == VQA_FP8_E4M3) return launch_dt<VQA_FP8_E4M3>(a, KT, lds, stream);
+    return launch_dt<VQA_F32>(a, KT, lds, stream);
 }
 
 #ifdef VQA_STAMPS

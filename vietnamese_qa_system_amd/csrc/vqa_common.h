@@ -169,8 +169,7 @@ struct ScoreTopkArgs {
     int32_t list_offset = 0;    // ... and the slot of this launch's workgroup 0 inside the row (two-stage search: the first
                                 // stage fills slots [0, grid), the main launch [grid, 2 grid) of rows of 2 grid lists)
     bool first_stage = false;   // the first-stage launch of a two-stage search: same code, its own kernel symbol
-    int32_t loop = 0;           // fp16: 0 = anti-phase slot loop, 1 = K-step-pair stagger loop (the fp8 structure); sketch scan: 1 = five
-                                // X ring stages instead of six
+    int32_t loop = 0;           // sketch scan: 1 = five X ring stages instead of six (the exact scans ignore it)
     const SketchScanArgs* sketch = nullptr;  // not null: MODE 2 over the int8 sketch (x = sketch rows, q = sketch of the query tile)
     bool regq = true;           // sketch scans: the register-resident-query kernel (scan_regq.hip) where it applies
     bool seed_only = false;  // MODE 0: writes seeds_per_tile sub-maxima per query and tile to `partial` as [query][tile - tile_begin][.]
