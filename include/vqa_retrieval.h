@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define VQA_VERSION 113 /* 0.1.13: vqa_index_options.sketch_regq (csrc/scan_regq.hip), .final_rescore, vqa_launch_info.scan_kernel, vqa_index_sketch_pause, vqa_index_search_filtered (detect it by its symbol); 0.1.12: vqa_index_options.one_launch (vqa_index_search_host of a small fp16 shard is one kernel); 0.1.11: vqa_encoder_forward_host, device queries in vqa_index_search_host; 0.1.10: vqa_index_search_host; 0.1.9: vqa_index_options / vqa_index_create_ex, vqa_encoder_options / vqa_encoder_create_ex (no environment variable is read any more), vqa_launch_info.levels; 0.1.8: vqa_encoder_forward_hidden; 0.1.7: vqa_index_get_sketch_split; 0.1.6: vqa_index_sketch_stats, vqa_index_get_sketch_tile; 0.1.5: vqa_index_sketch_state; 0.1.4: VQA_INDEX_RESCORE_ROWS, vqa_index_device_bytes; 0.1.3: VQA_INDEX_SKETCH */
+#define VQA_VERSION 113 /* 0.1.13: vqa_index_options.sketch_regq (csrc/scan_regq.hip), .final_rescore, vqa_launch_info.scan_kernel, vqa_index_sketch_pause, vqa_index_search_filtered, vqa_index_options.capacity, vqa_index_capacity, vqa_index_append_rows, vqa_index_remove_rows (detect them by their symbols); 0.1.12: vqa_index_options.one_launch (vqa_index_search_host of a small fp16 shard is one kernel); 0.1.11: vqa_encoder_forward_host, device queries in vqa_index_search_host; 0.1.10: vqa_index_search_host; 0.1.9: vqa_index_options / vqa_index_create_ex, vqa_encoder_options / vqa_encoder_create_ex (no environment variable is read any more), vqa_launch_info.levels; 0.1.8: vqa_encoder_forward_hidden; 0.1.7: vqa_index_get_sketch_split; 0.1.6: vqa_index_sketch_stats, vqa_index_get_sketch_tile; 0.1.5: vqa_index_sketch_state; 0.1.4: VQA_INDEX_RESCORE_ROWS, vqa_index_device_bytes; 0.1.3: VQA_INDEX_SKETCH */
 
 /* error codes */
 #define VQA_OK 0
@@ -131,6 +131,10 @@ typedef struct vqa_index_options {
                                    * overflow fallback) ends by scoring its rows in the sketch path's re-scoring arithmetic and re-ranking them,
                                    * so both paths return the same bits (k <= 10: over the scan's k + 2 best rows; rows that tie with the k-th
                                    * beyond those two can still differ); 0: the MFMA sums as they are */
+    int64_t capacity;             /* [0: n] rows the handle can hold (>= n): rows, ids, sketch, row-major copy and workspaces are allocated for
+                                   * `capacity` rows, and whether a sketch / copy is kept (and its size limits) is decided for `capacity`;
+                                   * vqa_index_append_rows grows n up to it.  What a search runs is decided per call from the current n: a
+                                   * sketch kept for the capacity is only searched while n has the size the sketch plan needs */
 } vqa_index_options;
 void vqa_index_options_init(vqa_index_options* opt);
 /* vqa_index_create with explicit options (`flags` travel inside them); opt == NULL: the defaults */
@@ -143,7 +147,27 @@ int vqa_index_set_rows(vqa_index* index, int64_t first, int64_t count, const voi
  * synchronises before returning. */
 int vqa_index_get_rows(vqa_index* index, int64_t first, int64_t count, void* out_rows, int64_t* out_ids_or_null);
 void vqa_index_destroy(vqa_index* index);
+
+/* ---- in-place updates (txtai's upsert / delete; faiss IndexIDMap add_with_ids / remove_ids).  Both take the handle like set_rows (one
+ * call at a time; VQA_EINVAL while a search is inside a call on it), run on the null stream and synchronise before returning.  A
+ * mutation changes n and moves rows: hipGraphs captured on the handle, and row bitmaps of vqa_index_search_filtered built for the old
+ * rows, no longer describe it and must be captured / built again.
+ * vqa_index_append_rows: rows [n, n + count) through the vqa_index_set_rows path (host or device rows, sketch re-cut, row-major copy,
+ * ids), then n += count.  n + count > capacity, ids given to a handle without an id vector or omitted for one with it: VQA_EINVAL,
+ * checked before any device work (the handle is unchanged).  The first rows of an empty handle fix the sketch's centre as a first
+ * vqa_index_set_rows does.
+ * vqa_index_remove_rows: removes the rows at the `count` distinct positions_host[] (host array, any order) by compaction, in a fixed
+ * number of launches however scattered they are (csrc/mutate.hip).  With n' = n - count: the removed positions below n', in ascending
+ * order, receive the surviving rows at positions >= n', in ascending order; every other row keeps its position; n becomes n'.  The
+ * rows [n', n) go back to zeros / id -1, the sketch of every tile a row moved into (and of the tile n' cuts) is cut again from the stored
+ * rows against the shard's fixed centre (the bits vqa_index_set_rows cuts for the same rows).  A position outside [0, n), a repeated
+ * one, positions_host NULL with count > 0, or a handle without an id vector (a moved row would report id_base + its new position):
+ * VQA_EINVAL before any device work, the handle unchanged.  Cost: the moved rows (read + write) plus the re-cut of the dirty tiles
+ * (256 rows each read, their codes written). */
+int vqa_index_append_rows(vqa_index* index, int64_t count, const void* rows, int32_t rows_dtype, const int64_t* ids_or_null);
+int vqa_index_remove_rows(vqa_index* index, const int64_t* positions_host, int64_t count);
 int64_t vqa_index_size(const vqa_index* index);
+int64_t vqa_index_capacity(const vqa_index* index); /* rows the handle can hold (vqa_index_options.capacity); -1: null */
 int32_t vqa_index_dim(const vqa_index* index);
 int32_t vqa_index_dtype(const vqa_index* index);
 /* device memory the shard holds: rows + id vector + sketch + re-scoring copy (workspaces of a few MB not counted); -1: null */

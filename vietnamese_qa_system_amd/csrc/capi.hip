@@ -58,6 +58,7 @@ static const PlanRules kPlan;
 struct vqa_index {
     int device = 0;
     int64_t n = 0;
+    int64_t capacity = 0;    // rows every row-sized allocation holds (options.capacity; n <= capacity): room for vqa_index_append_rows
     int32_t d = 0, d_pad = 0, dtype = 0;
     float scale = 1.0f;      // stored value = scale * given value (power of two; 16 for fp8 so unit-vector components leave
                              // the e4m3 subnormal range); queries are scaled alike and scores are multiplied by 1/scale^2
@@ -171,6 +172,11 @@ struct vqa_index {
     bool one_launch = true;   // options.one_launch: small fp16 shards answer vqa_index_search_host with ONE kernel (tiny_search.hip)
     void* tiny_ws = nullptr;  // its per-workgroup lists + ticket (lazy)
     std::atomic_flag busy = ATOMIC_FLAG_INIT;  // one search at a time per handle (the workspace is shared)
+    // vqa_index_remove_rows: its (src, dst) pairs and dirty tiles, uploaded once per call from a pinned staging buffer (lazy, grow-only)
+    void* mut_buf = nullptr;
+    void* mut_pinned = nullptr;      // host-mapped: the staging kernel reads it through mut_pinned_dev
+    void* mut_pinned_dev = nullptr;
+    size_t mut_bytes = 0;
 };
 
 constexpr int kSketchCap = 32768;  // candidate pairs per workgroup region / keys per query list (10M rows: ~1400 per query at k = 10,
@@ -231,6 +237,8 @@ extern "C" void vqa_index_destroy(vqa_index* ix) {
     if (ix->fin_scores) (void)hipFree(ix->fin_scores);
     if (ix->fin_ids) (void)hipFree(ix->fin_ids);
     if (ix->fin_pos) (void)hipFree(ix->fin_pos);
+    if (ix->mut_buf) (void)hipFree(ix->mut_buf);
+    if (ix->mut_pinned) (void)hipHostFree(ix->mut_pinned);
     for (hipEvent_t e : ix->ev) (void)hipEventDestroy(e);
     delete ix;
 }
@@ -303,6 +311,8 @@ static int upload_host_rows(vqa_index* ix, int64_t first, int64_t count, const v
     return VQA_OK;
 }
 
+static int set_rows_impl(vqa_index* ix, int64_t first, int64_t count, const void* rows, int32_t src_dtype, const int64_t* ids_or_null);
+
 extern "C" int vqa_index_set_rows(vqa_index* ix, int64_t first, int64_t count, const void* rows, int32_t src_dtype,
                                   const int64_t* ids_or_null) {
     VQA_REQUIRE(ix, "vqa_index_set_rows: index is null");
@@ -318,6 +328,12 @@ extern "C" int vqa_index_set_rows(vqa_index* ix, int64_t first, int64_t count, c
     // still in flight on a stream is the caller's to order: this call runs on the null stream and synchronises)
     HandleBusy busy(ix->busy);
     VQA_REQUIRE(busy.ok, "vqa_index_set_rows: this index handle is in use by another host thread (one call at a time per handle)");
+    return set_rows_impl(ix, first, count, rows, src_dtype, ids_or_null);
+}
+
+// rows [first, first + count) of [0, ix->n), arguments checked, the handle held by the caller: the stored rows, the sketch of every tile they
+// touch, the row-major copy and the ids
+static int set_rows_impl(vqa_index* ix, int64_t first, int64_t count, const void* rows, int32_t src_dtype, const int64_t* ids_or_null) {
     DeviceGuard guard(ix->device);
     hipPointerAttribute_t attr;
     bool on_device = hipPointerGetAttributes(&attr, rows) == hipSuccess && attr.type == hipMemoryTypeDevice;
@@ -407,6 +423,7 @@ extern "C" void vqa_index_options_init(vqa_index_options* o) {
     o->one_launch = 1;
     o->sketch_regq = 1;
     o->final_rescore = 1;
+    o->capacity = 0;
 }
 
 // -DVQA_DEV variant libraries only (scripts/: ab_loops.py, probes): the rounds-1-4 environment switches laid over the options
@@ -474,6 +491,10 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
                 "vqa_index_create_ex: a sketch_* option is negative");
     VQA_REQUIRE(o.poison_workspace >= -1 && o.poison_workspace <= 255, "vqa_index_create_ex: poison_workspace=%d", o.poison_workspace);
     VQA_REQUIRE(n >= 0 && n < 0xFFFFFFFFll, "vqa_index_create: n=%lld outside [0, 2^32-1) rows per shard", (long long)n);
+    VQA_REQUIRE(o.capacity == 0 || (o.capacity >= n && o.capacity < 0xFFFFFFFFll), "vqa_index_create_ex: capacity=%lld (0: n; else n .. 2^32-2)",
+                (long long)o.capacity);
+    // every allocation sized by rows, and every create-time decision that reads the row count, is made for `cap`; a search plans from n
+    const int64_t cap = o.capacity > 0 ? o.capacity : n;
     VQA_REQUIRE(d >= 1 && d <= 65536, "vqa_index_create: d=%d", d);
     VQA_REQUIRE(dtype == VQA_F32 || dtype == VQA_F16 || dtype == VQA_FP8_E4M3, "vqa_index_create: dtype %d", dtype);
     VQA_REQUIRE((flags & ~(uint32_t)(VQA_INDEX_HAS_IDS | VQA_INDEX_SKETCH | VQA_INDEX_RESCORE_ROWS)) == 0, "vqa_index_create: unknown flags 0x%x", flags);
@@ -497,6 +518,7 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
     }
     ix->device = device;
     ix->n = n;
+    ix->capacity = cap;
     ix->d = d;
     const int pad_to = 128 / elem_bytes(dtype);  // two K-steps of 64 bytes
     ix->d_pad = (d + pad_to - 1) / pad_to * pad_to;
@@ -519,9 +541,9 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
     const int eb = elem_bytes(dtype);
     int rc = VQA_OK;
     do {
-        const int64_t tiles = (n + 255) / 256;
+        const int64_t tiles = (cap + 255) / 256;
         ix->rows_bytes = (size_t)tiles * 256 * ix->d_pad * eb;
-        if (n > 0) {
+        if (cap > 0) {
             if (hipMalloc(&ix->rows, ix->rows_bytes) != hipSuccess) {
                 vqa_set_error("vqa_index_create: hipMalloc of %zu bytes for the rows failed", ix->rows_bytes);
                 rc = VQA_ENOMEM;
@@ -533,12 +555,14 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
                 rc = VQA_EHIP;
                 break;
             }
-            if ((ids_or_null || (flags & VQA_INDEX_HAS_IDS)) && hipMalloc((void**)&ix->ids, (size_t)n * 8) != hipSuccess) {
-                vqa_set_error("vqa_index_create: hipMalloc for %lld ids failed", (long long)n);
+            if ((ids_or_null || (flags & VQA_INDEX_HAS_IDS)) && hipMalloc((void**)&ix->ids, (size_t)cap * 8) != hipSuccess) {
+                vqa_set_error("vqa_index_create: hipMalloc for %lld ids failed", (long long)cap);
                 rc = VQA_ENOMEM;
                 break;
             }
-            if (ix->ids && !ids_or_null && hipMemset(ix->ids, 0xFF, (size_t)n * 8) != hipSuccess) {
+            // ids of rows no call has given yet are -1 (with ids_or_null: the rows past n)
+            const int64_t id0 = ids_or_null ? n : 0;
+            if (ix->ids && id0 < cap && hipMemset(ix->ids + id0, 0xFF, (size_t)(cap - id0) * 8) != hipSuccess) {
                 vqa_set_error("vqa_index_create: clearing the ids failed");
                 rc = VQA_EHIP;
                 break;
@@ -552,7 +576,7 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
             hipMalloc((void**)&ix->thr_seed, VQA_QUERY_TILE * sizeof(float)) != hipSuccess ||
             hipMalloc((void**)&ix->upper, VQA_QUERY_TILE * sizeof(vqa_key)) != hipSuccess ||
             hipMalloc((void**)&ix->wide_flag, sizeof(int)) != hipSuccess ||
-            hipMalloc((void**)&ix->flt_tiles, ((size_t)tiles + 1 + vqa_filter_chunks(n)) * sizeof(int)) != hipSuccess ||
+            hipMalloc((void**)&ix->flt_tiles, ((size_t)tiles + 1 + vqa_filter_chunks(cap)) * sizeof(int)) != hipSuccess ||
             ((dtype == VQA_F16 || dtype == VQA_F32) &&
              (hipMalloc((void**)&ix->fin_scores, (size_t)VQA_QUERY_TILE * VQA_MAX_K_TOTAL * 4) != hipSuccess ||
               hipMalloc((void**)&ix->fin_ids, (size_t)VQA_QUERY_TILE * VQA_MAX_K_TOTAL * 8) != hipSuccess ||
@@ -570,7 +594,8 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
         // fp16 shards: the cascade pays from 16 tiles per compute unit (1.05M rows) on -- 1.5M rows: 0.56 vs 0.65 ms, 1M: 0.48 either
         // way, 0.5M: 0.30 vs 0.27 (the exact two-stage plan of shards without a sketch keeps its 24)
         if ((flags & VQA_INDEX_SKETCH) && dtype == VQA_F16 && !stage_given) ix->stage_min_tiles = kPlan.stage_min_f16_sketch;
-        ix->sketch = (flags & VQA_INDEX_SKETCH) && (dtype == VQA_F16 || dtype == VQA_F32) && n > 0 && ix->stage_min_tiles > 0 &&
+        // (whether the sketch APPLIES is decided per search, from n: sketch_active)
+        ix->sketch = (flags & VQA_INDEX_SKETCH) && (dtype == VQA_F16 || dtype == VQA_F32) && cap > 0 && ix->stage_min_tiles > 0 &&
                      tiles >= (int64_t)ix->stage_min_tiles * ix->max_grid &&
                      (tiles + ix->max_grid - 1) / ix->max_grid <= vqa_score_topk_sketch_max_tiles() && d <= 8192;
         if (ix->sketch) {
@@ -664,7 +689,7 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
             (void)hipMemset(ix->thr0, byte, VQA_QUERY_TILE * sizeof(float));
             (void)hipMemset(ix->thr_seed, byte, VQA_QUERY_TILE * sizeof(float));
             (void)hipMemset(ix->upper, byte, VQA_QUERY_TILE * sizeof(vqa_key));
-            (void)hipMemset(ix->flt_tiles, byte, ((size_t)((n + 255) / 256) + 1 + vqa_filter_chunks(n)) * sizeof(int));
+            (void)hipMemset(ix->flt_tiles, byte, ((size_t)tiles + 1 + vqa_filter_chunks(cap)) * sizeof(int));
             if (ix->sketch) {
                 (void)hipMemset(ix->qrow, byte, 5 * VQA_QUERY_TILE * sizeof(float));
                 (void)hipMemset(ix->qconst, byte, kSketchQRows * VQA_QUERY_TILE * sizeof(float));
@@ -730,7 +755,110 @@ extern "C" int vqa_index_get_rows(vqa_index* ix, int64_t first, int64_t count, v
     return VQA_OK;
 }
 
+// ---- in-place updates: rows [n, n + count) through the set_rows path, and removal by compaction (mutate.hip)
+extern "C" int vqa_index_append_rows(vqa_index* ix, int64_t count, const void* rows, int32_t src_dtype, const int64_t* ids_or_null) {
+    VQA_REQUIRE(ix, "vqa_index_append_rows: index is null");
+    VQA_REQUIRE(count >= 0 && count <= ix->capacity - ix->n, "vqa_index_append_rows: %lld rows onto %lld exceed the capacity of %lld",
+                (long long)count, (long long)ix->n, (long long)ix->capacity);
+    VQA_REQUIRE(src_dtype == VQA_F32 || src_dtype == VQA_F16, "vqa_index_append_rows: source element type %d is not f32/f16", src_dtype);
+    VQA_REQUIRE((ids_or_null != nullptr) == (ix->ids != nullptr) || count == 0,
+                "vqa_index_append_rows: the index was created %s an id vector", ix->ids ? "with" : "without");
+    if (count == 0) return VQA_OK;
+    VQA_REQUIRE(rows, "vqa_index_append_rows: rows is null");
+    HandleBusy busy(ix->busy);
+    VQA_REQUIRE(busy.ok, "vqa_index_append_rows: this index handle is in use by another host thread (one call at a time per handle)");
+    const int64_t n0 = ix->n;
+    ix->n = n0 + count;  // (the sketch of the tiles the new rows touch is cut for the new n)
+    const int rc = set_rows_impl(ix, n0, count, rows, src_dtype, ids_or_null);
+    if (rc != VQA_OK) ix->n = n0;
+    return rc;
+}
+
+extern "C" int vqa_index_remove_rows(vqa_index* ix, const int64_t* positions, int64_t count) {
+    VQA_REQUIRE(ix, "vqa_index_remove_rows: index is null");
+    VQA_REQUIRE(ix->ids, "vqa_index_remove_rows: the index has no id vector (a moved row would report id_base + its new position)");
+    VQA_REQUIRE(count >= 0 && count <= ix->n, "vqa_index_remove_rows: count=%lld of %lld rows", (long long)count, (long long)ix->n);
+    VQA_REQUIRE(positions || count == 0, "vqa_index_remove_rows: positions is null");
+    if (count == 0) return VQA_OK;
+    std::vector<int64_t> rm(positions, positions + count);
+    std::sort(rm.begin(), rm.end());
+    VQA_REQUIRE(rm.front() >= 0 && rm.back() < ix->n, "vqa_index_remove_rows: a position outside [0, %lld)", (long long)ix->n);
+    VQA_REQUIRE(std::adjacent_find(rm.begin(), rm.end()) == rm.end(), "vqa_index_remove_rows: a position is given twice");
+    HandleBusy busy(ix->busy);
+    VQA_REQUIRE(busy.ok, "vqa_index_remove_rows: this index handle is in use by another host thread (one call at a time per handle)");
+    DeviceGuard guard(ix->device);
+    // the rule (include/vqa_retrieval.h): the holes below n' in ascending order take the surviving rows at >= n' in ascending order
+    const int64_t n = ix->n, n1 = n - count;
+    const size_t holes = (size_t)(std::lower_bound(rm.begin(), rm.end(), n1) - rm.begin());
+    std::vector<int64_t> buf(2 * holes);
+    size_t j = holes, m = 0;
+    for (int64_t p = n1; p < n; ++p) {
+        if (j < rm.size() && rm[j] == p) ++j;
+        else buf[m++] = p;
+    }
+    std::copy(rm.begin(), rm.begin() + holes, buf.begin() + holes);
+    // dirty tiles: those the holes lie in, and the one n' cuts (tiles wholly past n' are vacated: no search reads them)
+    const size_t tiles0 = buf.size();
+    for (size_t i = 0; i < holes; ++i) {
+        const int64_t t = rm[i] >> 8;
+        if (buf.size() == tiles0 || buf.back() != t) buf.push_back(t);
+    }
+    if ((n1 & 255) && (buf.size() == tiles0 || buf.back() != (n1 >> 8))) buf.push_back(n1 >> 8);
+    const int64_t ntiles = (int64_t)(buf.size() - tiles0);
+    const size_t bytes = buf.size() * 8;
+    if (ix->mut_bytes < bytes) {
+        if (ix->mut_buf) (void)hipFree(ix->mut_buf);
+        if (ix->mut_pinned) (void)hipHostFree(ix->mut_pinned);
+        ix->mut_buf = ix->mut_pinned = ix->mut_pinned_dev = nullptr;
+        ix->mut_bytes = 0;
+        const size_t want = std::max<size_t>(bytes, 64 << 10);
+        if (hipMalloc(&ix->mut_buf, want) != hipSuccess || hipHostMalloc(&ix->mut_pinned, want, hipHostMallocMapped) != hipSuccess ||
+            hipHostGetDevicePointer(&ix->mut_pinned_dev, ix->mut_pinned, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            vqa_set_error("vqa_index_remove_rows: hipMalloc of %zu bytes failed", want);
+            return VQA_ENOMEM;
+        }
+        ix->mut_bytes = want;
+    }
+    int64_t* dbuf = static_cast<int64_t*>(ix->mut_buf);
+    // (copied by a kernel from mapped pinned memory, on the null stream in front of the launches: a copy-engine DMA -- hipMemcpy or
+    // hipMemcpyAsync -- paid 6-12 ms of one-time setup inside the call on the first removal of a process)
+    memcpy(ix->mut_pinned, buf.data(), bytes);
+    int rc = vqa_launch_stage_words(static_cast<const int64_t*>(ix->mut_pinned_dev), (int64_t)buf.size(), dbuf, nullptr);
+    if (rc != VQA_OK) return rc;
+    const int row_units = ix->d_pad * elem_bytes(ix->dtype) / 16;
+    rc = vqa_launch_move_rows(dbuf, dbuf + holes, (int64_t)holes, ix->rows, row_units, ix->rows_rm, ix->ids, nullptr);
+    if (rc != VQA_OK) return rc;
+    rc = vqa_launch_clear_rows(n1, count, ix->rows, row_units, ix->rows_rm, ix->sketch ? ix->rows8 : nullptr, ix->d_pad8 / 16,
+                               ix->sketch ? ix->beta : nullptr, ix->ids, nullptr);
+    if (rc != VQA_OK) return rc;
+    if (ix->sketch) {
+        // the dirty tiles' sketch, cut by set_rows' own quantiser against the shard's fixed centre; vacated tiles back to create's zeros
+        const int64_t* tl = dbuf + tiles0;
+        rc = vqa_launch_tile_scales_list(ix->rows, ix->dtype, tl, ntiles, ix->d_pad, ix->d_pad8, ix->tile_info, ix->rotate, ix->center ? ix->mu : nullptr,
+                                         ix->tile_c, ix->per_row ? ix->wdir : nullptr, nullptr);
+        if (rc != VQA_OK) return rc;
+        SketchSplit sp;
+        sp.wdir = ix->wdir;
+        sp.tile_c = ix->tile_c;
+        sp.per_row = ix->per_row ? 1 : 0;
+        sp.beta = ix->per_row ? ix->beta : nullptr;
+        rc = vqa_launch_sketch_rows_list(ix->rows, ix->dtype, tl, ntiles, n1, ix->d_pad, ix->d_pad8, ix->tile_info, ix->rows8, ix->rotate,
+                                         ix->center ? ix->mu : nullptr, ix->wdir ? &sp : nullptr, nullptr);
+        if (rc != VQA_OK) return rc;
+        const int64_t v0 = (n1 + 255) / 256, v1 = (n + 255) / 256;
+        if (v1 > v0) {
+            VQA_HIP_CHECK(hipMemsetAsync(ix->tile_info + 4 * v0, 0, (size_t)(v1 - v0) * 16, nullptr));
+            VQA_HIP_CHECK(hipMemsetAsync(ix->tile_c + v0, 0, (size_t)(v1 - v0) * 4, nullptr));
+        }
+    }
+    ix->n = n1;
+    VQA_HIP_CHECK(hipStreamSynchronize(nullptr));
+    return VQA_OK;
+}
+
 extern "C" int64_t vqa_index_size(const vqa_index* ix) { return ix ? ix->n : -1; }
+extern "C" int64_t vqa_index_capacity(const vqa_index* ix) { return ix ? ix->capacity : -1; }
 extern "C" int32_t vqa_index_dim(const vqa_index* ix) { return ix ? ix->d : -1; }
 extern "C" int32_t vqa_index_dtype(const vqa_index* ix) { return ix ? ix->dtype : -1; }
 // the profitability rule of the sketch search (vqa_index::profit_ratio)
@@ -769,8 +897,8 @@ extern "C" int vqa_index_sketch_pause(vqa_index* ix, int32_t searches) {
 
 extern "C" int64_t vqa_index_device_bytes(const vqa_index* ix) {
     if (!ix) return -1;
-    int64_t b = (int64_t)ix->rows_bytes + (ix->ids ? ix->n * 8 : 0);
-    if (ix->sketch) b += (int64_t)ix->rows8_bytes + ((ix->n + 255) / 256) * 16;
+    int64_t b = (int64_t)ix->rows_bytes + (ix->ids ? ix->capacity * 8 : 0);
+    if (ix->sketch) b += (int64_t)ix->rows8_bytes + ((ix->capacity + 255) / 256) * 16;
     if (ix->rows_rm) b += (int64_t)ix->rows_bytes;
     return b;
 }
@@ -855,6 +983,12 @@ static LaunchPlan plan_launch(const vqa_index* ix, int k = 0) {
 static bool final_rescore_applies(const vqa_index* ix, const LaunchPlan& p) {
     return ix->final_fma && ix->fin_pos && (ix->dtype == VQA_F16 || ix->dtype == VQA_F32) && ix->scale == 1.0f && ix->fin_min_tiles > 0 &&
            (long long)p.tiles >= (long long)ix->fin_min_tiles * ix->max_grid;
+}
+
+// the shard keeps a sketch AND has, at its current n, the size at which create would have kept one: a handle whose capacity kept a
+// sketch but whose rows are fewer plans like a handle created for those rows (capacity == n: exactly ix->sketch)
+static bool sketch_sized(const vqa_index* ix) {
+    return ix->sketch && (ix->n + 255) / 256 >= (int64_t)ix->stage_min_tiles * ix->max_grid;
 }
 
 static bool sketch_active(const vqa_index* ix, const LaunchPlan& p, int k) {
@@ -1059,7 +1193,7 @@ extern "C" int vqa_index_search_host(vqa_index* ix, const void* q_host, int32_t 
     const size_t need = p_off + nres * 8;
     // one launch for the whole call where K4 applies (tiny_search.hip); `timing` handles time the scan kernel of the general path
     // (a shard on the two-stage plan -- only tests bring that down to this size -- answers in the re-scoring arithmetic: the general launches)
-    const bool one_launch = ix->one_launch && !ix->timing && !ix->sketch && ix->scale == 1.0f && vqa_tiny_search_applies(ix->dtype, ix->n, ix->d_pad, B, k) &&
+    const bool one_launch = ix->one_launch && !ix->timing && !sketch_sized(ix) && ix->scale == 1.0f && vqa_tiny_search_applies(ix->dtype, ix->n, ix->d_pad, B, k) &&
                             !final_rescore_applies(ix, plan_launch(ix, k));
     if (one_launch && !ix->tiny_ws) {
         const size_t ws = vqa_tiny_search_workspace_bytes();

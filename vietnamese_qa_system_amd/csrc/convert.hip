@@ -51,11 +51,7 @@ __device__ __forceinline__ uint8_t f32_to_e4m3(float f) {
 // reads 1 KiB contiguous per wave-instruction and a tile's K-steps stream from HBM as one sequential 256 * d_pad * esize
 // byte run.  Which k index lands in which byte of a unit is irrelevant as long as rows and queries agree (a dot product
 // is invariant under a common permutation of k), so elements are simply stored in their natural order.
-__device__ __forceinline__ size_t tiled_unit(long long row, int kappa, int slot, int KT) {
-    const long long t = row >> 8;
-    const int r = (int)(row & 255);
-    return ((size_t)t * KT + kappa) * 1024 + (size_t)(r * 4 + (slot ^ (((r >> 3) & 1) * 3)));
-}
+__device__ __forceinline__ size_t tiled_unit(long long row, int kappa, int slot, int KT) { return vqa_tiled_unit(row, kappa, slot, KT); }
 
 template <typename DST>
 __device__ __forceinline__ DST store_cast(float v);
@@ -260,17 +256,15 @@ struct QueryStage {
     void* rowmajor = nullptr;   // [256][KTS * 64 bytes] or nullptr
 };
 
+// The sketch of ONE row per wave: row `row` of the array (output slot ri of the per-row outputs).  The body of sketch_rows_kernel (rows of a
+// contiguous range) and sketch_rows_list_kernel (the rows of listed tiles: a removal's dirty tiles, mutate.hip) -- one quantiser.
 template <typename SRC, bool ROT, int NG>
-__global__ __launch_bounds__(256) void sketch_rows_kernel(const SRC* __restrict__ tiled, long long first, long long count,
-                                                          int KTS, int KT8, const float* tile_info, int8_t* __restrict__ out8,
-                                                          float* __restrict__ row_scale, float* __restrict__ row_lo,
-                                                          float* __restrict__ row_norm, unsigned* tile_max /* = tile_info */,
-                                                          const float* __restrict__ mu, int center, float* __restrict__ row_off,
-                                                          QueryStage qs, SketchSplit sp) {
+__device__ __forceinline__ void sketch_row_body(const SRC* __restrict__ tiled, long long ri, long long row, int KTS, int KT8,
+                                                const float* tile_info, int8_t* __restrict__ out8, float* __restrict__ row_scale,
+                                                float* __restrict__ row_lo, float* __restrict__ row_norm, unsigned* tile_max,
+                                                const float* __restrict__ mu, int center, float* __restrict__ row_off,
+                                                QueryStage qs, SketchSplit sp) {
     const int lane = threadIdx.x & 63;
-    const long long ri = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (ri >= count) return;
-    const long long row = first + ri;
     const int units8 = KT8 * 4;
     // this lane's int8 units u = lane, lane + 64, ...
     constexpr int kMaxPer = NG;
@@ -457,15 +451,37 @@ __global__ __launch_bounds__(256) void sketch_rows_kernel(const SRC* __restrict_
     }
 }
 
+template <typename SRC, bool ROT, int NG>
+__global__ __launch_bounds__(256) void sketch_rows_kernel(const SRC* __restrict__ tiled, long long first, long long count,
+                                                          int KTS, int KT8, const float* tile_info, int8_t* __restrict__ out8,
+                                                          float* __restrict__ row_scale, float* __restrict__ row_lo,
+                                                          float* __restrict__ row_norm, unsigned* tile_max /* = tile_info */,
+                                                          const float* __restrict__ mu, int center, float* __restrict__ row_off,
+                                                          QueryStage qs, SketchSplit sp) {
+    const long long ri = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ri >= count) return;
+    sketch_row_body<SRC, ROT, NG>(tiled, ri, first + ri, KTS, KT8, tile_info, out8, row_scale, row_lo, row_norm, tile_max, mu, center, row_off,
+                                  qs, sp);
+}
+
+// index rows of the LISTED tiles (64 workgroups of 4 waves per tile), rows at positions >= n skipped: their codes stay as they are (zeros)
+template <typename SRC, bool ROT, int NG>
+__global__ __launch_bounds__(256) void sketch_rows_list_kernel(const SRC* __restrict__ tiled, const long long* __restrict__ tiles, long long n,
+                                                               int KTS, int KT8, const float* tile_info, int8_t* __restrict__ out8,
+                                                               unsigned* tile_max, const float* __restrict__ mu, SketchSplit sp) {
+    const long long row = tiles[blockIdx.x >> 6] * 256 + (blockIdx.x & 63) * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    sketch_row_body<SRC, ROT, NG>(tiled, row, row, KTS, KT8, tile_info, out8, nullptr, nullptr, nullptr, tile_max, mu, 1, nullptr, QueryStage(), sp);
+}
+
 // one workgroup per tile of a TILED fp16 / fp32 array: scale = max |x| over the tile's 256 rows / 127 (a tile of zeros: 1), written
 // with its reciprocal to tile_info[tile] = (0, 0, 1 / scale, scale) -- the two maxima are cleared for sketch_rows_kernel to fill
+// (the body, for one tile: tile_scale_kernel takes a contiguous range of tiles, tile_scale_list_kernel listed ones)
 template <typename SRC, bool ROT, int NG>
-__global__ __launch_bounds__(256) void tile_scale_kernel(const SRC* __restrict__ tiled, long long tile0, int KTS, int KT8,
-                                                         float* __restrict__ tile_info, const float* __restrict__ mu,
-                                                         float* __restrict__ tile_c, const float* __restrict__ proj_w) {
+__device__ __forceinline__ void tile_scale_body(const SRC* __restrict__ tiled, long long tile, int KTS, int KT8, float* __restrict__ tile_info,
+                                                const float* __restrict__ mu, float* __restrict__ tile_c, const float* __restrict__ proj_w) {
     constexpr int EPU = 16 / (int)sizeof(SRC);
     __shared__ float red[4];
-    const long long tile = tile0 + blockIdx.x;
     float m = 0.f;
     if constexpr (ROT) {  // the maximum is that of the ROTATED rows: every wave rotates 64 of the tile's rows
         const int lane = threadIdx.x & 63, units8 = KT8 * 4;
@@ -536,6 +552,20 @@ __global__ __launch_bounds__(256) void tile_scale_kernel(const SRC* __restrict__
         o[3] = s;
         if (tile_c) tile_c[tile] = 0.f;
     }
+}
+
+template <typename SRC, bool ROT, int NG>
+__global__ __launch_bounds__(256) void tile_scale_kernel(const SRC* __restrict__ tiled, long long tile0, int KTS, int KT8,
+                                                         float* __restrict__ tile_info, const float* __restrict__ mu,
+                                                         float* __restrict__ tile_c, const float* __restrict__ proj_w) {
+    tile_scale_body<SRC, ROT, NG>(tiled, tile0 + blockIdx.x, KTS, KT8, tile_info, mu, tile_c, proj_w);
+}
+
+template <typename SRC, bool ROT, int NG>
+__global__ __launch_bounds__(256) void tile_scale_list_kernel(const SRC* __restrict__ tiled, const long long* __restrict__ tiles, int KTS, int KT8,
+                                                              float* __restrict__ tile_info, const float* __restrict__ mu,
+                                                              float* __restrict__ tile_c, const float* __restrict__ proj_w) {
+    tile_scale_body<SRC, ROT, NG>(tiled, tiles[blockIdx.x], KTS, KT8, tile_info, mu, tile_c, proj_w);
 }
 
 // w = T mu / ||T mu|| (zeros when the centre is zero): the direction the slack term of the bound is split along (sketch_rows_kernel); one wave
@@ -763,6 +793,70 @@ int vqa_launch_tile_scales(const void* tiled, int32_t src_dtype, int64_t tile0, 
     }
 #undef VQA_TSCALE
 #undef VQA_TSCALE_NG
+    VQA_HIP_CHECK(hipGetLastError());
+    return VQA_OK;
+}
+
+// The re-cut of LISTED tiles (a removal's dirty tiles, mutate.hip): tile_scale_body and sketch_row_body, the bodies of the two launches above,
+// over a device list of tile indices -- the bits vqa_launch_tile_scales + vqa_launch_sketch_rows cut for the same stored rows
+int vqa_launch_tile_scales_list(const void* tiled, int32_t src_dtype, const int64_t* tiles, int64_t ntiles, int32_t d_pad_src, int32_t d_pad8,
+                                float* tile_info, bool rotate, const float* mu, float* tile_c, const float* proj_w, hipStream_t stream) {
+    if (ntiles == 0) return VQA_OK;
+    VQA_REQUIRE(tiles && (rotate || (!proj_w && !mu)), "tile_scales_list: bad arguments");
+    const long long* tl = reinterpret_cast<const long long*>(tiles);
+#define VQA_TSLIST_NG(T, ROT, NGV, KTSV)                                                                                          \
+    hipLaunchKernelGGL((tile_scale_list_kernel<T, ROT, NGV>), dim3((unsigned)ntiles), dim3(256), 0, stream, reinterpret_cast<const T*>(tiled), \
+                       tl, KTSV, d_pad8 / 64, tile_info, mu, tile_c, proj_w)
+#define VQA_TSLIST(T, ROT, KTSV)                                                                                                  \
+    do {                                                                                                                          \
+        if (d_pad8 <= 1024) VQA_TSLIST_NG(T, ROT, 1, KTSV);                                                                       \
+        else if (d_pad8 <= 2048) VQA_TSLIST_NG(T, ROT, 2, KTSV);                                                                  \
+        else if (d_pad8 <= 4096) VQA_TSLIST_NG(T, ROT, 4, KTSV);                                                                  \
+        else VQA_TSLIST_NG(T, ROT, 8, KTSV);                                                                                      \
+    } while (0)
+    if (src_dtype == VQA_F16) {
+        if (rotate) VQA_TSLIST(_Float16, true, d_pad_src / 32);
+        else VQA_TSLIST(_Float16, false, d_pad_src / 32);
+    } else {
+        if (rotate) VQA_TSLIST(float, true, d_pad_src / 16);
+        else VQA_TSLIST(float, false, d_pad_src / 16);
+    }
+#undef VQA_TSLIST
+#undef VQA_TSLIST_NG
+    VQA_HIP_CHECK(hipGetLastError());
+    return VQA_OK;
+}
+
+int vqa_launch_sketch_rows_list(const void* tiled, int32_t src_dtype, const int64_t* tiles, int64_t ntiles, int64_t n, int32_t d_pad_src,
+                                int32_t d_pad8, float* tile_info, void* out8, bool rotate, const float* mu, const SketchSplit* split,
+                                hipStream_t stream) {
+    if (ntiles == 0) return VQA_OK;
+    VQA_REQUIRE(tiles && tile_info && out8 && (src_dtype == VQA_F16 || src_dtype == VQA_F32) && d_pad8 / 16 <= 8 * 64,
+                "sketch_rows_list: bad arguments");
+    VQA_REQUIRE(ntiles <= (1ll << 25), "sketch_rows_list: %lld tiles", (long long)ntiles);
+    const SketchSplit sp = split ? *split : SketchSplit();
+    const long long* tl = reinterpret_cast<const long long*>(tiles);
+    unsigned* tmax = reinterpret_cast<unsigned*>(tile_info);
+    const dim3 grid((unsigned)(ntiles * 64));
+#define VQA_SKLIST_NG(T, ROT, NGV, KTSV)                                                                                          \
+    hipLaunchKernelGGL((sketch_rows_list_kernel<T, ROT, NGV>), grid, dim3(256), 0, stream, reinterpret_cast<const T*>(tiled), tl, (long long)n, \
+                       KTSV, d_pad8 / 64, tile_info, reinterpret_cast<int8_t*>(out8), tmax, mu, sp)
+#define VQA_SKLIST(T, ROT, KTSV)                                                                                                  \
+    do {                                                                                                                          \
+        if (d_pad8 <= 1024) VQA_SKLIST_NG(T, ROT, 1, KTSV);                                                                       \
+        else if (d_pad8 <= 2048) VQA_SKLIST_NG(T, ROT, 2, KTSV);                                                                  \
+        else if (d_pad8 <= 4096) VQA_SKLIST_NG(T, ROT, 4, KTSV);                                                                  \
+        else VQA_SKLIST_NG(T, ROT, 8, KTSV);                                                                                      \
+    } while (0)
+    if (src_dtype == VQA_F16) {
+        if (rotate) VQA_SKLIST(_Float16, true, d_pad_src / 32);
+        else VQA_SKLIST(_Float16, false, d_pad_src / 32);
+    } else {
+        if (rotate) VQA_SKLIST(float, true, d_pad_src / 16);
+        else VQA_SKLIST(float, false, d_pad_src / 16);
+    }
+#undef VQA_SKLIST
+#undef VQA_SKLIST_NG
     VQA_HIP_CHECK(hipGetLastError());
     return VQA_OK;
 }

@@ -78,6 +78,15 @@ __host__ __device__ __forceinline__ vqa_key vqa_make_key(float score, uint32_t p
 __host__ __device__ __forceinline__ float vqa_key_score(vqa_key k) { return vqa_ordered_f32((uint32_t)(k >> 32)); }
 __host__ __device__ __forceinline__ uint32_t vqa_key_pos(vqa_key k) { return 0xFFFFFFFFu - (uint32_t)k; }
 
+// TILED layout of the index rows (convert.hip writes it, mutate.hip moves rows in it): unit (16 B) of (row, K-block kappa, slot) in an
+// array of KT K-blocks of 64 bytes per row -- tile row >> 8 is KT contiguous blocks of 16 KiB, inside a block the unit of (r, slot) sits
+// at r * 4 + (slot ^ 3 * bit3(r)): the bank-conflict-free LDS image the scans load
+__device__ __forceinline__ size_t vqa_tiled_unit(long long row, int kappa, int slot, int KT) {
+    const long long t = row >> 8;
+    const int r = (int)(row & 255);
+    return ((size_t)t * KT + kappa) * 1024 + (size_t)(r * 4 + (slot ^ (((r >> 3) & 1) * 3)));
+}
+
 // Largest key of the wave, in every lane.  Four DPP steps inside each row of 16 lanes (quad_perm xor 1, xor 2, row_half_mirror,
 // row_mirror: the partner's two halves arrive with one VALU move each), then v_permlane16_swap / v_permlane32_swap of a register
 // with itself across the rows -- no LDS crossbar (six 64-bit __shfl_xor steps are twelve dependent ds_bpermute round trips, which
@@ -286,6 +295,21 @@ int vqa_launch_row_mean(const void* tiled, int32_t src_dtype, int64_t first, int
 int vqa_launch_tile_scales(const void* tiled, int32_t src_dtype, int64_t tile0, int64_t ntiles, int32_t d_pad_src, int32_t d_pad8,
                            float* tile_info, bool rotate, const float* mu, hipStream_t stream, float* tile_c = nullptr /* cleared too */,
                            const float* proj_w = nullptr /* per-row form: the scale of y - (w . y) w */);
+// the same two launches over a DEVICE list of tile indices (int64 [ntiles]); rows at positions >= n are not sketched (mutate.hip: a removal's
+// dirty tiles)
+int vqa_launch_tile_scales_list(const void* tiled, int32_t src_dtype, const int64_t* tiles, int64_t ntiles, int32_t d_pad_src, int32_t d_pad8,
+                                float* tile_info, bool rotate, const float* mu, float* tile_c, const float* proj_w, hipStream_t stream);
+int vqa_launch_sketch_rows_list(const void* tiled, int32_t src_dtype, const int64_t* tiles, int64_t ntiles, int64_t n, int32_t d_pad_src,
+                                int32_t d_pad8, float* tile_info, void* out8, bool rotate, const float* mu, const SketchSplit* split,
+                                hipStream_t stream);
+// mutate.hip: rows src[i] -> dst[i] (16-byte units of the TILED rows, their row-major copy or nullptr, ids) for i < pairs, one launch; then
+// rows [first, first + count) back to what create leaves (zeros in rows, copy, int8 sketch (units8 16-byte units per row) and beta; id -1)
+// `words` int64 of host-mapped pinned memory (its device address) -> device memory, by a kernel (mutate.hip)
+int vqa_launch_stage_words(const int64_t* mapped, int64_t words, int64_t* out, hipStream_t stream);
+int vqa_launch_move_rows(const int64_t* src, const int64_t* dst, int64_t pairs, void* rows, int32_t row_units, void* rows_rm, int64_t* ids,
+                         hipStream_t stream);
+int vqa_launch_clear_rows(int64_t first, int64_t count, void* rows, int32_t row_units, void* rows_rm, void* rows8, int32_t units8, float* beta,
+                          int64_t* ids, hipStream_t stream);
 // sketch search: per-query constants of the scan + reset of the candidate counters; exact scores of the candidate pairs
 int vqa_launch_sketch_qconst(const float* thr, const float* qscale, const float* qlo, const float* qnorm, int32_t d, float* qconst,
                              unsigned* cand_cnt, int* overflow /* [4]: this tile's flag, OR over the call's earlier tiles, seq, pairs scored exactly */,

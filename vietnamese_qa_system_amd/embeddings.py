@@ -33,7 +33,7 @@ import torch.distributed as dist
 
 from . import _native as N
 from . import docstore
-from .index import _STORE_NP, DeviceIndex, resolve_dtype
+from .index import _STORE_NP, DeviceIndex, compaction_moves, resolve_dtype
 from .rowfilter import RowFilter
 from .sharded import ShardedSearcher, shard_bounds
 from .sparse import BM25Index, combine
@@ -101,6 +101,8 @@ class Embeddings:
         self._shard_ids: Optional[np.ndarray] = None  # host copy of this shard's id vector (filters by id / by document field)
         self._allow: Optional[RowFilter] = None  # the shard's filter of the search in progress (_local_search)
         self.load_stats: Optional[dict] = None  # filled by load(): bytes, seconds, GB/s of the file -> HBM stream
+        self._mutable = False                   # upsert / delete happened: the shard carries an id vector of stable integer keys
+        self._docs_over: Optional[dict] = None  # loaded index: key -> upserted document (None: deleted) over documents.db
         self.n = 0
         self.d = 0
 
@@ -198,6 +200,7 @@ class Embeddings:
           ``documents`` then cover either this rank's rows or the whole corpus (told apart by their length).
         """
         self._host_ids = None  # ids of an earlier index() on this object must not leak into the new one
+        self._mutable, self._docs_over, self._host_pos = False, None, None
         producer = vectors if callable(vectors) else None
         if producer is not None:
             if total is None:
@@ -312,7 +315,8 @@ class Embeddings:
         wanted = list(flt)
         if self._host_ids is not None:
             pos = getattr(self, "_host_pos", None)
-            if pos is None or len(pos) != len(self._host_ids):
+            # (an updated index keeps _host_pos itself, with holes in _host_ids where ids were deleted: never rebuilt from them)
+            if pos is None or (not self._mutable and len(pos) != len(self._host_ids)):
                 pos = self._host_pos = {h: p for p, h in enumerate(self._host_ids)}
             return np.asarray([pos[i] for i in wanted if i in pos], dtype=np.int64)
         return np.asarray([int(i) for i in wanted if isinstance(i, (int, np.integer)) and not isinstance(i, bool)], dtype=np.int64)
@@ -340,7 +344,13 @@ class Embeddings:
                     out += [int(r[0]) for r in conn.execute(f"SELECT id FROM documents WHERE {column} IN ({marks})", chunk)]
             finally:
                 conn.close()
-            return np.unique(np.asarray(out, dtype=np.int64))
+            got = np.unique(np.asarray(out, dtype=np.int64))
+            if self._docs_over:  # documents upserted / deleted since load(): they replace the file's rows
+                over = np.fromiter(self._docs_over.keys(), dtype=np.int64, count=len(self._docs_over))
+                vs = set(values)
+                hit = [k for k, doc in self._docs_over.items() if doc is not None and doc.get(field) in vs]
+                got = np.union1d(got[~np.isin(got, over)], np.asarray(hit, dtype=np.int64))
+            return got
         raise ValueError("a filter by document field needs stored documents (content=True)")
 
     def _shard_mask(self, device_ids: np.ndarray) -> np.ndarray:
@@ -393,7 +403,210 @@ class Embeddings:
         return self._format(scores.cpu().numpy(), ids.cpu().numpy())
 
     def count(self) -> int:
+        """Rows of the index (after upsert / delete: the live ones)."""
         return self.n
+
+    # ---- in-place updates (txtai upsert / delete) ---------------------------------------------------------------------
+    def upsert(self, documents: Iterable, batch_size: int = 512) -> None:
+        """txtai ``upsert``: documents in any form :meth:`index` takes; an id already in the index is overwritten in place (its row and
+        document), new ids are added.  A document without an id (a bare string, a dict without "id") is NEW: it gets the next unused
+        integer id after every id the index has held (never its position in this call, which would overwrite another row); an index with
+        string ids refuses it.  The encoder runs on the upserted documents only."""
+        raw = list(documents)
+        docs = self._normalise_documents(raw)
+        if not docs:
+            return
+        has_id = [isinstance(r, (tuple, list)) or (isinstance(r, dict) and "id" in r) for r in raw]
+        if not all(has_id) and self._host_ids is not None and self.world == 1 and self._index is not None:
+            raise ValueError("this index has string ids: every upserted document needs its id")
+        self._check_mutable(extra=len(docs))
+        if not all(has_id):
+            given = [d["id"] for d, h in zip(docs, has_id) if h and isinstance(d["id"], (int, np.integer)) and not isinstance(d["id"], bool)]
+            nxt = max([self._next_key] + [int(i) + 1 for i in given])
+            for d, h in zip(docs, has_id):
+                if not h:
+                    d["id"], nxt = nxt, nxt + 1
+        texts = [str(d.get("text", "")) for d in docs]
+        vecs = torch.cat([self._encode(texts[c0:c0 + batch_size]).float() for c0 in range(0, len(texts), max(int(batch_size), 1))])
+        self._upsert(list(d["id"] for d in docs), vecs, docs, texts)
+
+    def upsert_vectors(self, ids: Sequence, vectors, documents: Optional[List[dict]] = None) -> None:
+        """:meth:`upsert` with precomputed embeddings ``vectors`` [len(ids), d] (the counterpart of :meth:`index_vectors`); ``documents``
+        (content=True, or the texts of a hybrid index) one per id."""
+        self._check_mutable(extra=len(ids))
+        v = torch.from_numpy(np.ascontiguousarray(vectors)) if isinstance(vectors, np.ndarray) else vectors
+        if v.dim() != 2 or int(v.shape[0]) != len(ids) or int(v.shape[1]) != self.d:
+            raise ValueError(f"vectors must be [{len(ids)}, {self.d}]")
+        if documents is not None and len(documents) != len(ids):
+            raise ValueError(f"{len(documents)} documents for {len(ids)} ids")
+        if self.hybrid and self._sparse is not None and documents is None:
+            raise ValueError("a hybrid index needs the documents (their texts) of upserted rows")
+        texts = [str(d.get("text", "")) for d in documents] if documents is not None else None
+        self._upsert(list(ids), v, documents, texts)
+
+    def delete(self, ids: Iterable) -> list:
+        """txtai ``delete``: removes the rows of ``ids`` (unknown ids are ignored) and returns the ids actually deleted.  Removal
+        compacts the shard in place (``DeviceIndex.remove``): the last rows fill the holes, nothing is re-encoded."""
+        self._check_mutable()
+        ids = list(ids)
+        keys, ext = self._keys_of(ids, create=False)
+        pos, found = self._positions_of(keys)
+        if not found.any():
+            return []
+        pos, first = np.unique(pos[found], return_index=True)
+        gone_keys, gone_ext = keys[found][first], [e for e, f in zip(ext, found) if f]
+        gone_ext = list(dict.fromkeys(gone_ext))  # (an id named twice is deleted once)
+        n0 = self._index.n
+        self._index.remove(pos)
+        src, dst = compaction_moves(n0, pos)
+        keep = np.ones(n0, dtype=bool)
+        keep[pos] = False
+        self._shard_ids[dst] = self._shard_ids[src]
+        self._shard_ids = self._shard_ids[:n0 - pos.size].copy()
+        self._row_ids = self._shard_ids
+        self._forget_documents(gone_keys)
+        if self._host_ids is not None:
+            for k in gone_keys.tolist():
+                self._host_pos.pop(self._host_ids[k], None)
+                self._host_ids[k] = None
+        if self._sparse is not None:
+            pmap = np.full(n0, -1, dtype=np.int64)
+            pmap[np.flatnonzero(keep)] = np.flatnonzero(keep)
+            pmap[src] = dst
+            self._sparse.update(pmap, n0 - pos.size)
+        self.n = self._index.n
+        return gone_ext
+
+    def _check_mutable(self, extra: int = 0) -> None:
+        """First update of this index: the shard moves to a device id vector of stable keys.  ``extra``: rows the calling update may add,
+        so that a shard rebuilt for its id vector is rebuilt at the capacity the update needs (one copy, not two)."""
+        if self.world > 1:
+            # (new rows would have to be placed across the ranks' shards: a collective protocol of its own)
+            raise NotImplementedError("upsert / delete on a sharded index (torch.distributed with more than one rank) is not supported")
+        if self._index is None:
+            raise RuntimeError("the index is empty: call index()/load() first")
+        if self._mutable:
+            return
+        # first mutation: every row gets an explicit, stable integer key in a device id vector (contiguous ids and ids=None too: deleting
+        # row 5 must not renumber the rows behind it); string ids keep theirs on the host, key -> id
+        ix = self._index
+        keys = self._shard_ids if ix.has_ids else ix.id_base + np.arange(ix.n, dtype=np.int64)
+        if not ix.has_ids:
+            need = ix.n + int(extra)
+            self._rebuild(ix.capacity if need <= ix.capacity else max(2 * ix.capacity, need), keys)
+        self._shard_ids = np.asarray(keys, dtype=np.int64).copy()
+        self._row_ids = self._shard_ids
+        if self._host_ids is not None:
+            self._host_ids = list(self._host_ids)
+            self._host_pos = {h: k for k, h in enumerate(self._host_ids) if h is not None}
+        if self._docs_db is not None:
+            self._docs_over = {}
+        elif self._docs_mem is not None:
+            self._docs_rows = self._docs_mem.items()
+        # upserted documents without an id get keys from here on (past every key the index has held; string ids: the next host slot)
+        self._next_key = int(self._shard_ids.max()) + 1 if self._shard_ids.size else 0
+        self._mutable = True
+
+    def _rebuild(self, capacity: int, keys: np.ndarray, chunk_rows: int = 1 << 20) -> None:
+        """A new handle for ``capacity`` rows with an id vector of ``keys``, filled from the old one device to device (get_rows into a
+        device buffer, append), chunk by chunk; the old handle is closed afterwards."""
+        old = self._index
+        dev = torch.device("cuda", self.device)
+        new = DeviceIndex.empty(0, self.d, dtype=self.dtype, device=self.device, with_ids=True, capacity=max(int(capacity), 1))
+        store_t = {N.VQA_F32: torch.float32, N.VQA_F16: torch.float16, N.VQA_FP8_E4M3: torch.uint8}[old.dtype]
+        decode = None
+        if old.dtype == N.VQA_FP8_E4M3:  # stored e4m3 codes of 16 x -> x as fp16 (exact), which append re-encodes to the same codes
+            from .index import FP8_SCALE
+            decode = torch.from_numpy((_e4m3_decode_table() / FP8_SCALE).astype(np.float16)).to(dev)
+        keys_t = torch.from_numpy(np.ascontiguousarray(keys, dtype=np.int64))
+        buf = torch.empty((min(chunk_rows, max(old.n, 1)), self.d), dtype=store_t, device=dev)
+        for c0 in range(0, old.n, chunk_rows):
+            c = min(chunk_rows, old.n - c0)
+            old.get_rows(c0, c, out=buf[:c])
+            rows = decode[buf[:c].long()] if decode is not None else buf[:c]
+            new.append(rows, ids=keys_t[c0:c0 + c])
+        old.close()
+        self._index = new
+
+    def _keys_of(self, ids: list, create: bool):
+        """External ids -> (int64 device keys, the ids they stand for).  Unknown string ids get new keys when ``create``, else are
+        dropped."""
+        if self._host_ids is not None:
+            keys, ext = [], []
+            for h in ids:
+                k = self._host_pos.get(h)
+                if k is None and create:
+                    k = self._host_pos[h] = len(self._host_ids)
+                    self._host_ids.append(h)
+                if k is not None:
+                    keys.append(k)
+                    ext.append(h)
+            return np.asarray(keys, dtype=np.int64), ext
+        ext = [i for i in ids if isinstance(i, (int, np.integer)) and not isinstance(i, bool)]
+        if create and len(ext) != len(ids):
+            raise ValueError("this index has integer ids: every upserted id must be an integer")
+        return np.asarray(ext, dtype=np.int64), ext
+
+    def _positions_of(self, keys: np.ndarray):
+        """(shard positions, found mask) of ``keys`` in the shard's key vector (sorted lookup, no loop over the corpus)."""
+        sk = self._shard_ids
+        order = np.argsort(sk, kind="stable")
+        j = np.searchsorted(sk[order], keys)
+        jc = np.minimum(j, max(sk.size - 1, 0))
+        found = (j < sk.size) & (sk[order][jc] == keys) if sk.size else np.zeros(keys.shape, dtype=bool)
+        return np.where(found, order[jc] if sk.size else 0, -1), found
+
+    def _forget_documents(self, keys: np.ndarray) -> None:
+        if self._docs_over is not None:
+            self._docs_over.update((int(k), None) for k in keys.tolist())
+        elif self._docs_mem is not None:
+            for k in keys.tolist():
+                self._docs_mem.pop(int(k), None)
+
+    def _upsert(self, ids: list, v: torch.Tensor, documents: Optional[List[dict]], texts: Optional[List[str]]) -> None:
+        if not ids:
+            return
+        keys, _ = self._keys_of(ids, create=True)
+        if keys.size:
+            self._next_key = max(self._next_key, int(keys.max()) + 1)
+        # the last occurrence of a repeated id wins
+        _, last = np.unique(keys[::-1], return_index=True)
+        sel = np.sort(keys.size - 1 - last)
+        keys = keys[sel]
+        v = v[torch.from_numpy(sel)] if sel.size != v.shape[0] else v
+        docs = [documents[i] for i in sel.tolist()] if documents is not None else None
+        texts = [texts[i] for i in sel.tolist()] if texts is not None else None
+        normalize = self.normalize and v.dtype == torch.float32
+        pos, found = self._positions_of(keys)
+        n0 = self._index.n
+        # existing ids: overwritten where they are, one set_rows per run of consecutive positions
+        if found.any():
+            fi = np.flatnonzero(found)
+            fi = fi[np.argsort(pos[fi], kind="stable")]
+            fp = pos[fi]
+            cuts = np.flatnonzero(np.diff(fp) != 1) + 1
+            for run in np.split(np.arange(fi.size), cuts):
+                idx = torch.from_numpy(fi[run])
+                self._index.set_rows(int(fp[run[0]]), v[idx], torch.from_numpy(keys[fi[run]]), normalize=normalize)
+        new = np.flatnonzero(~found)
+        if new.size:
+            if n0 + new.size > self._index.capacity:
+                self._rebuild(max(2 * self._index.capacity, n0 + new.size), self._shard_ids)
+            self._index.append(v[torch.from_numpy(new)], ids=torch.from_numpy(keys[new]), normalize=normalize)
+            self._shard_ids = np.concatenate([self._shard_ids, keys[new]])
+            self._row_ids = self._shard_ids
+        if docs is not None and self.content:
+            store = self._docs_over if self._docs_over is not None else self._docs_mem
+            if store is None:
+                store = self._docs_mem = {}
+                self._docs_rows = self._docs_mem.items()
+            store.update((int(k), d) for k, d in zip(keys.tolist(), docs))
+        if self._sparse is not None and texts is not None:
+            pmap = np.arange(n0, dtype=np.int64)
+            pmap[pos[found]] = -1  # overwritten rows: their postings are replaced by the new text's
+            at = np.concatenate([pos[found], n0 + np.arange(new.size)])
+            self._sparse.update(pmap, n0 + new.size, added=(at, [texts[i] for i in np.flatnonzero(found).tolist() + new.tolist()]))
+        self.n = self._index.n
 
     # ---- searching ------------------------------------------------------------------------------------------------
     def _query_vectors(self, queries) -> torch.Tensor:
@@ -594,6 +807,8 @@ class Embeddings:
             wanted = ids[keep].tolist()
             if self._docs_db is not None:
                 texts = docstore.fetch_docs(self._docs_db, wanted)
+                if self._docs_over:
+                    texts.update({i: (self._docs_over[i] or {}).get("text") for i in set(wanted) if i in self._docs_over})
             elif self._docs_mem is not None:
                 texts = {i: self._docs_mem[i].get("text") for i in set(wanted) if i in self._docs_mem}
         # plain Python lists first: per-element numpy indexing costs more than the GPU search of a 256-query batch
@@ -699,8 +914,20 @@ class Embeddings:
                     # one row per corpus row, keyed by what the device reports for it (row position for string ids)
                     docstore.write_documents(db, [{"id": key, "text": doc.get("text"), "source": doc.get("source")}
                                                   for key, doc in docs_rows])
-                elif self._docs_db is not None and os.path.abspath(self._docs_db) != os.path.abspath(db):
-                    shutil.copyfile(self._docs_db, db)  # a loaded index keeps its documents on re-save
+                elif self._docs_db is not None:
+                    if os.path.abspath(self._docs_db) != os.path.abspath(db):
+                        shutil.copyfile(self._docs_db, db)  # a loaded index keeps its documents on re-save
+                    if self._docs_over:  # ... with the documents upserted / deleted since load() merged in
+                        gone = [k for k, doc in self._docs_over.items() if doc is None]
+                        import sqlite3
+                        conn = sqlite3.connect(db)
+                        try:
+                            with conn:
+                                conn.executemany("DELETE FROM documents WHERE id = ?", [(int(k),) for k in gone])
+                        finally:
+                            conn.close()
+                        docstore.write_documents(db, [{"id": k, "text": doc.get("text"), "source": doc.get("source")}
+                                                      for k, doc in self._docs_over.items() if doc is not None])
         if self.world > 1:
             dist.barrier(group=self.group)
 
@@ -721,6 +948,7 @@ class Embeddings:
             self.encoder, self._auto_encoder_path = None, None  # built from the path of ANOTHER model: the loaded index names its own
         self.path, self.content, self.hybrid = meta["path"], meta["content"], meta["hybrid"]
         self._host_ids = meta.get("host_ids")
+        self._mutable, self._docs_over, self._host_pos = False, None, None
         lo, hi = shard_bounds(n, self.world, self.rank)
         vec_dtype = meta.get("vector_dtype", "float16")
         np_dtype = np.dtype(vec_dtype)
@@ -744,10 +972,10 @@ class Embeddings:
         self._docs_mem = self._docs_rows = None
         self.weights = float(meta.get("weights", 0.5))
         self._sparse = BM25Index.load(path) if self.hybrid else None
-        if self._host_ids is not None:
+        if meta["has_ids"]:  # (string ids with an id vector: an updated index, its keys index host_ids)
+            self._row_ids = np.fromfile(os.path.join(path, IDS_FILE), dtype=np.int64) if self.hybrid or self._host_ids is not None else None
+        elif self._host_ids is not None:
             self._row_ids = np.arange(n, dtype=np.int64)
-        elif meta["has_ids"]:
-            self._row_ids = np.fromfile(os.path.join(path, IDS_FILE), dtype=np.int64) if self.hybrid else None
         else:
             self._row_ids = np.arange(n, dtype=np.int64) + int(meta["id_base"])
         return self

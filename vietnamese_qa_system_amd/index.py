@@ -46,6 +46,25 @@ def resolve_dtype(dtype) -> int:
         raise ValueError(f"unknown index dtype {dtype!r}; expected one of {sorted(N.DTYPE_NAMES)}") from None
 
 
+def compaction_moves(n: int, positions) -> Tuple[np.ndarray, np.ndarray]:
+    """The row moves of removing ``positions`` (distinct, in ``[0, n)``, any order) from a shard of ``n`` rows -- the rule of
+    ``vqa_index_remove_rows`` (include/vqa_retrieval.h): with ``n' = n - len(positions)``, the removed positions below ``n'`` in
+    ascending order (``dst``) receive the surviving rows at positions ``>= n'`` in ascending order (``src``); every other row keeps
+    its position.  Returns ``(src, dst)`` int64 arrays of equal length; a host mirror applies them as ``a[dst] = a[src]; a = a[:n']``."""
+    n = int(n)
+    p = np.sort(np.asarray(positions, dtype=np.int64).reshape(-1))
+    if p.size and (int(p[0]) < 0 or int(p[-1]) >= n):
+        raise ValueError(f"row positions outside [0, {n})")
+    if p.size > 1 and bool((p[1:] == p[:-1]).any()):
+        raise ValueError("a row position is given twice")
+    n1 = n - int(p.size)
+    dst = p[p < n1]
+    keep = np.ones(n - n1, dtype=bool)
+    keep[p[p >= n1] - n1] = False
+    src = n1 + np.flatnonzero(keep).astype(np.int64)
+    return src, dst
+
+
 def _as_tensor(a, what: str) -> torch.Tensor:
     t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
     if not isinstance(t, torch.Tensor):
@@ -63,11 +82,15 @@ class DeviceIndex:
     AUTOINCREMENT rowids start at 1, ``setup_db.py:14``).  ``DeviceIndex.empty(n, d)`` + :meth:`set_rows` fills a
     large shard chunk by chunk without a second full copy.  ``options``: fields of ``vqa_index_options`` by name (A/B runs and
     tests; production passes none).
+
+    In-place updates: ``capacity`` (>= n; default n) rows are allocated, :meth:`append` adds rows up to it and :meth:`remove`
+    takes rows out by compaction (:func:`compaction_moves` states where the survivors go; it needs an id vector).  Both advance
+    :attr:`generation`, which makes the :class:`RowFilter` objects built before them stale.
     """
 
     def __init__(self, vectors=None, ids=None, *, id_base: int = 0, dtype="fp16", device: int = 0, normalize: bool = False,
                  n: Optional[int] = None, d: Optional[int] = None, with_ids: Optional[bool] = None, sketch: Optional[bool] = None,
-                 rescore_copy: Optional[bool] = None, options: Optional[dict] = None):
+                 rescore_copy: Optional[bool] = None, options: Optional[dict] = None, capacity: Optional[int] = None):
         self._handle = ctypes.c_void_p()
         self.device = int(device)
         _require_gpu(self.device)
@@ -97,8 +120,12 @@ class DeviceIndex:
             rescore_copy = bool(opts["rescore_copy"])
         elif rescore_copy is not None:
             opts["rescore_copy"] = 1 if rescore_copy else 0
+        if capacity is not None:
+            if int(capacity) < int(n):
+                raise ValueError(f"capacity {capacity} < n = {n}")
+            opts["capacity"] = int(capacity)
         if rescore_copy is None:
-            rescore_copy = int(n) * int(d) * N.DTYPE_BYTES[self.dtype] <= RESCORE_COPY_MAX_BYTES
+            rescore_copy = max(int(n), int(opts.get("capacity", 0))) * int(d) * N.DTYPE_BYTES[self.dtype] <= RESCORE_COPY_MAX_BYTES
         if rescore_copy and (flags & N.VQA_INDEX_SKETCH):
             flags |= N.VQA_INDEX_RESCORE_ROWS
         self.options = N.index_options(flags, **opts)
@@ -107,15 +134,18 @@ class DeviceIndex:
                                                   N.VQA_F16, None, int(id_base), ctypes.byref(self.options)),
                     "vqa_index_create_ex")
         self.n, self.d, self.id_base, self.has_ids = int(n), int(d), int(id_base), has_ids
+        self.capacity = int(self._lib.vqa_index_capacity(self._handle))
+        self.generation = 0  # advanced by every append / remove (RowFilters record the one they were built at)
         if vectors is not None and n:
             self.set_rows(0, v, ids, normalize=normalize)
 
     @classmethod
     def empty(cls, n: int, d: int, *, id_base: int = 0, dtype="fp16", device: int = 0, with_ids: bool = False,
-              sketch: Optional[bool] = None, rescore_copy: Optional[bool] = None, options: Optional[dict] = None) -> "DeviceIndex":
-        """A shard of ``n`` zero rows to be filled with :meth:`set_rows`."""
+              sketch: Optional[bool] = None, rescore_copy: Optional[bool] = None, options: Optional[dict] = None,
+              capacity: Optional[int] = None) -> "DeviceIndex":
+        """A shard of ``n`` zero rows to be filled with :meth:`set_rows` (room for ``capacity`` rows)."""
         return cls(None, None, id_base=id_base, dtype=dtype, device=device, n=n, d=d, with_ids=with_ids, sketch=sketch,
-                   rescore_copy=rescore_copy, options=options)
+                   rescore_copy=rescore_copy, options=options, capacity=capacity)
 
     # -- filling -------------------------------------------------------------------------------------------------
     def set_rows(self, first: int, vectors, ids=None, *, normalize: bool = False, chunk_rows: int = 1 << 20) -> None:
@@ -130,6 +160,38 @@ class DeviceIndex:
         count = int(v.shape[0])
         if first < 0 or first + count > self.n:
             raise ValueError(f"rows [{first}, {first + count}) outside the shard of {self.n} rows")
+        self._write(first, v, ids, normalize, chunk_rows, append=False)
+
+    def append(self, vectors, ids=None, *, normalize: bool = False, chunk_rows: int = 1 << 20) -> None:
+        """Rows [n, n + count) from ``vectors`` [count, d] (``vqa_index_append_rows``); ``ids`` exactly when the shard has an id
+        vector.  Raises ``ValueError`` past :attr:`capacity`, with the shard unchanged."""
+        if not self._handle.value:
+            raise RuntimeError("index is closed")
+        v = _as_tensor(vectors, "vectors")
+        if v.dim() != 2 or int(v.shape[1]) != self.d:
+            raise ValueError(f"vectors must be [count, {self.d}]")
+        if v.dtype not in _SRC_DTYPE:
+            raise ValueError(f"vectors must be float32 or float16, got {v.dtype}")
+        if self.n + int(v.shape[0]) > self.capacity:
+            raise ValueError(f"{int(v.shape[0])} rows onto {self.n} exceed the capacity of {self.capacity}")
+        self._write(self.n, v, ids, normalize, chunk_rows, append=True)
+        self.generation += 1
+
+    def remove(self, positions) -> None:
+        """Take the rows at ``positions`` (distinct shard positions, host or device, any order) out by compaction
+        (``vqa_index_remove_rows``; where the survivors go: :func:`compaction_moves`).  Needs an id vector."""
+        if not self._handle.value:
+            raise RuntimeError("index is closed")
+        p = positions.cpu().numpy() if isinstance(positions, torch.Tensor) else positions
+        p = np.ascontiguousarray(np.asarray(p, dtype=np.int64).reshape(-1))
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream(self.device).synchronize()  # (the call runs on the null stream)
+            N.check(self._lib.vqa_index_remove_rows(self._handle, p.ctypes.data if p.size else None, int(p.size)), "vqa_index_remove_rows")
+        self.n -= int(p.size)
+        self.generation += 1
+
+    def _write(self, first: int, v: torch.Tensor, ids, normalize: bool, chunk_rows: int, append: bool) -> None:
+        count = int(v.shape[0])
         ids_t = None
         if ids is not None:
             ids_t = _as_tensor(ids, "ids").to(torch.int64).contiguous()
@@ -154,19 +216,33 @@ class DeviceIndex:
                 chunk_ids = ids_t[c0:c1].contiguous() if ids_t is not None else None
                 if rows.is_cuda:
                     torch.cuda.current_stream(rows.device).synchronize()  # set_rows runs on the null stream
-                N.check(self._lib.vqa_index_set_rows(self._handle, first + c0, c1 - c0, rows.data_ptr(), _SRC_DTYPE[rows.dtype],
-                                                     chunk_ids.data_ptr() if chunk_ids is not None else None),
-                        "vqa_index_set_rows")
+                ids_ptr = chunk_ids.data_ptr() if chunk_ids is not None else None
+                if append:
+                    N.check(self._lib.vqa_index_append_rows(self._handle, c1 - c0, rows.data_ptr(), _SRC_DTYPE[rows.dtype], ids_ptr),
+                            "vqa_index_append_rows")
+                    self.n += c1 - c0
+                else:
+                    N.check(self._lib.vqa_index_set_rows(self._handle, first + c0, c1 - c0, rows.data_ptr(), _SRC_DTYPE[rows.dtype],
+                                                         ids_ptr), "vqa_index_set_rows")
 
     def get_rows(self, first: int = 0, count: Optional[int] = None,
                  out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """Stored rows [first, first + count) as a host array [count, d] in the storage type (``float16``, ``float32`` or
         ``uint8`` e4m3 codes of ``16 * x``) and their ids, if the index has an id vector -- the export used by
         ``Embeddings.save``.  ``out``: a C-contiguous host array of that shape and type to fill (a pinned one makes the
-        device -> host copy a DMA)."""
+        device -> host copy a DMA), or a contiguous tensor on this device (the rows are copied device to device; no ids)."""
         if not self._handle.value:
             raise RuntimeError("index is closed")
         count = self.n - first if count is None else int(count)
+        if isinstance(out, torch.Tensor):  # a device buffer: the rows stay on the device (Embeddings grows a shard this way)
+            want = {np.float16: torch.float16, np.float32: torch.float32, np.uint8: torch.uint8}[_STORE_NP[self.dtype]]
+            if (tuple(out.shape) != (count, self.d) or out.dtype != want or not out.is_contiguous() or not out.is_cuda
+                    or out.device.index != self.device):
+                raise ValueError(f"out must be a contiguous {want} tensor of shape {(count, self.d)} on cuda:{self.device}")
+            torch.cuda.current_stream(self.device).synchronize()  # (the call runs on the null stream)
+            N.check(self._lib.vqa_index_get_rows(self._handle, int(first), count, out.data_ptr() if count else None, None),
+                    "vqa_index_get_rows")
+            return out, None
         if out is not None:
             if out.shape != (count, self.d) or out.dtype != _STORE_NP[self.dtype] or not out.flags["C_CONTIGUOUS"]:
                 raise ValueError(f"out must be a C-contiguous {_STORE_NP[self.dtype]} array of shape {(count, self.d)}")
@@ -202,8 +278,11 @@ class DeviceIndex:
         if mask is not None:
             if int(mask.shape[0]) != self.n:
                 raise ValueError(f"a row mask of this shard has {self.n} entries, got {int(mask.shape[0])}")
-            return RowFilter.from_mask(mask, device=self.device)
-        return RowFilter.from_positions(self.n, positions, device=self.device)
+            flt = RowFilter.from_mask(mask, device=self.device)
+        else:
+            flt = RowFilter.from_positions(self.n, positions, device=self.device)
+        flt.generation = self.generation
+        return flt
 
     def search(self, queries: torch.Tensor, k: int, *, return_positions: bool = False,
                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, allow: Optional[RowFilter] = None
@@ -232,6 +311,9 @@ class DeviceIndex:
         if allow is not None:
             if not isinstance(allow, RowFilter) or allow.n != self.n:
                 raise ValueError(f"allow must be a RowFilter of this shard's {self.n} rows")
+            if allow.generation is not None and allow.generation != self.generation:
+                raise ValueError(f"the RowFilter was built at generation {allow.generation} of this shard, which has changed since "
+                                 f"(generation {self.generation}): build it again with row_filter()")
             if allow.bits.device != dev:
                 raise ValueError(f"the RowFilter lives on {allow.bits.device}, the shard on {dev}: build it with row_filter()")
         with torch.cuda.device(dev):

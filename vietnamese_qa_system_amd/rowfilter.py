@@ -52,6 +52,7 @@ class RowFilter:
             raise ValueError(f"bits must be an int32 [{(n + 31) // 32}] tensor for {n} rows")
         self.bits = bits.contiguous()
         self.n = n
+        self.generation = None  # DeviceIndex.row_filter(): the shard's generation it was built at (a later append / remove makes it stale)
         mask = bits_to_mask(self.bits, n)
         self.allowed = int(mask.sum().item())
         pad = torch.zeros((-n) % TILE_ROWS, dtype=torch.bool, device=mask.device)
@@ -98,6 +99,7 @@ class RowFilter:
             return self
         out = RowFilter.__new__(RowFilter)
         out.bits, out.n, out.allowed, out.tiles = self.bits.to(dev), self.n, self.allowed, self.tiles
+        out.generation = self.generation
         return out
 
     def __repr__(self) -> str:

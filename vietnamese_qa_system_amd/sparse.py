@@ -86,6 +86,54 @@ class BM25Index:
         self.avgscore = self._score(avgfreq, avgidf, self.avgdl) if n else 0.0
         return self
 
+    def update(self, pmap: np.ndarray, n: int, added: Optional[Tuple[np.ndarray, List[str]]] = None) -> "BM25Index":
+        """The index after rows moved, left or were rewritten (Embeddings.upsert / delete): row position p becomes ``pmap[p]`` (-1: its
+        postings are dropped), the index has ``n`` rows, and ``added`` = (positions, texts) gives the rows whose text is (re)indexed.  The
+        postings are remapped with numpy and the statistics recomputed: O(corpus postings) per call -- what rebuilding from the texts
+        costs, without keeping them; terms no row holds any more leave the vocabulary, so scores are those of a fresh index of the same texts
+        (up to the order of floating-point sums)."""
+        pmap = np.asarray(pmap, np.int64)
+        terms = np.repeat(np.arange(len(self.idf), dtype=np.int64), np.diff(self.indptr))
+        rows = pmap[self.docs] if self.docs.size else self.docs
+        live = rows >= 0
+        terms, rows, tf = terms[live], rows[live], self.tf[live]
+        doclen = np.zeros(n, np.float32)
+        kept = np.flatnonzero(pmap >= 0)
+        doclen[pmap[kept]] = self.doclen[kept]
+        vocab = dict(self.vocab)
+        if added is not None:
+            at, texts = added
+            t_new, r_new, c_new = [], [], []
+            for p, text in zip(np.asarray(at, np.int64).tolist(), texts):
+                toks = self.tokenizer(text)
+                doclen[p] = len(toks)
+                local: Dict[int, int] = {}
+                for t in toks:
+                    tid = vocab.setdefault(t, len(vocab))
+                    local[tid] = local.get(tid, 0) + 1
+                t_new += list(local.keys())
+                r_new += [p] * len(local)
+                c_new += list(local.values())
+            terms = np.concatenate([terms, np.asarray(t_new, np.int64)])
+            rows = np.concatenate([rows, np.asarray(r_new, np.int64)])
+            tf = np.concatenate([tf, np.asarray(c_new, np.float32)])
+        df = np.bincount(terms, minlength=len(vocab)).astype(np.int64)
+        alive = df > 0  # the vocabulary a fresh index of these texts would have
+        remap = np.cumsum(alive) - 1
+        words = sorted(vocab, key=vocab.get)
+        self.vocab = {w: int(remap[i]) for i, w in enumerate(words) if alive[i]}
+        terms, df = remap[terms], df[alive]
+        order = np.lexsort((rows, terms))
+        self.docs, self.tf, self.doclen = rows[order], tf[order], doclen
+        self.indptr = np.concatenate([[0], np.cumsum(df)]).astype(np.int64)
+        self.idf = np.log(1.0 + (n - df + 0.5) / (df + 0.5)).astype(np.float32)
+        self.avgdl = float(doclen.mean()) if n else 0.0
+        v = len(self.vocab)
+        avgfreq = float(doclen.sum()) / v if v else 0.0
+        avgidf = float(self.idf.mean()) if v else 0.0
+        self.avgscore = self._score(avgfreq, avgidf, self.avgdl) if n else 0.0
+        return self
+
     def _score(self, tf, idf, dl):
         norm = self.k1 * (1.0 - self.b + self.b * (dl / self.avgdl if self.avgdl > 0 else 1.0))
         return idf * tf * (self.k1 + 1.0) / (tf + norm)
