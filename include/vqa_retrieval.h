@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define VQA_VERSION 113 /* 0.1.13: vqa_index_options.sketch_regq (csrc/scan_regq.hip), .final_rescore, vqa_launch_info.scan_kernel, vqa_index_sketch_pause, vqa_index_search_filtered, vqa_index_options.capacity, vqa_index_capacity, vqa_index_append_rows, vqa_index_remove_rows (detect them by their symbols); 0.1.12: vqa_index_options.one_launch (vqa_index_search_host of a small fp16 shard is one kernel); 0.1.11: vqa_encoder_forward_host, device queries in vqa_index_search_host; 0.1.10: vqa_index_search_host; 0.1.9: vqa_index_options / vqa_index_create_ex, vqa_encoder_options / vqa_encoder_create_ex (no environment variable is read any more), vqa_launch_info.levels; 0.1.8: vqa_encoder_forward_hidden; 0.1.7: vqa_index_get_sketch_split; 0.1.6: vqa_index_sketch_stats, vqa_index_get_sketch_tile; 0.1.5: vqa_index_sketch_state; 0.1.4: VQA_INDEX_RESCORE_ROWS, vqa_index_device_bytes; 0.1.3: VQA_INDEX_SKETCH */
+#define VQA_VERSION 113 /* 0.1.13: vqa_index_options.sketch_regq (csrc/scan_regq.hip), .final_rescore, vqa_launch_info.scan_kernel, vqa_index_sketch_pause, vqa_index_search_filtered, vqa_index_options.capacity, vqa_index_capacity, vqa_index_append_rows, vqa_index_remove_rows, vqa_index_search_filtered_multi (detect them by their symbols); 0.1.12: vqa_index_options.one_launch (vqa_index_search_host of a small fp16 shard is one kernel); 0.1.11: vqa_encoder_forward_host, device queries in vqa_index_search_host; 0.1.10: vqa_index_search_host; 0.1.9: vqa_index_options / vqa_index_create_ex, vqa_encoder_options / vqa_encoder_create_ex (no environment variable is read any more), vqa_launch_info.levels; 0.1.8: vqa_encoder_forward_hidden; 0.1.7: vqa_index_get_sketch_split; 0.1.6: vqa_index_sketch_stats, vqa_index_get_sketch_tile; 0.1.5: vqa_index_sketch_state; 0.1.4: VQA_INDEX_RESCORE_ROWS, vqa_index_device_bytes; 0.1.3: VQA_INDEX_SKETCH */
 
 /* error codes */
 #define VQA_OK 0
@@ -245,6 +245,19 @@ int vqa_index_search(vqa_index* index, const void* q, int32_t q_dtype, int32_t B
  * bitmap returns the bits of vqa_index_search on the same handle. */
 int vqa_index_search_filtered(vqa_index* index, const void* q, int32_t q_dtype, int32_t B, int32_t k, const uint32_t* allow_bits,
                               float* out_scores, int64_t* out_ids, int64_t* out_pos_or_null, void* hip_stream);
+
+/* Filtered search with one bitmap per query: query b of the batch is restricted to its own set of rows.  allow_bits: DEVICE
+ * [F][ceil(n / 32)] words, F >= 1 bitmaps of the layout above, back to back; query_filter: DEVICE [B] int32, the bitmap of each
+ * query -- f in [0, F) searches the rows of bitmap f, -1 searches all rows, any other value searches none (its results are all
+ * padding; the library cannot read the array without a synchronisation, so it defines rather than checks these values).  Results,
+ * ties, padding, bits past n, k, B, asynchrony (capturable; a replay follows what both arrays hold at replay time), the sketch and
+ * the final re-scoring: as vqa_index_search_filtered -- a query returns the bits of that call with its own bitmap.  NULL or host
+ * allow_bits / query_filter, F < 1, and a bad B, k or q_dtype are VQA_EINVAL before any device work.
+ * Cost: per query tile (256 queries) the scan reads the tiles of the UNION of its queries' bitmaps (one -1 entry: every tile) and
+ * masks per (row, query); the compaction reads each bitmap the tile uses once (bitmaps used x n / 8 bytes, twice), not one per query. */
+int vqa_index_search_filtered_multi(vqa_index* index, const void* q, int32_t q_dtype, int32_t B, int32_t k, const uint32_t* allow_bits,
+                                    int32_t F, const int32_t* query_filter, float* out_scores, int64_t* out_ids, int64_t* out_pos_or_null,
+                                    void* hip_stream);
 
 /* The latency form of vqa_index_search for the reference's own calling pattern -- one question per call, limit = 1
  * (heavy_ranker.py:97-101): HOST pointers in and out, synchronous.  q_host [B, d] fp32 / fp16 host memory; normalize = 1 (fp32

@@ -94,6 +94,7 @@ struct vqa_index {
     int* wide_flag = nullptr;    // 1 = the one-pass large-k result could not be verified: the gated continuation passes run
     int* flt_tiles = nullptr;    // filtered search: [ceil(n / 256)] tiles holding an allowed row, then [1] their count, then
                                  // [vqa_filter_chunks(n)] per-chunk counts of the compaction (filter.hip)
+    int* flt_qmap = nullptr;     // one bitmap per query: the query tile's map of MODE 4 ([kFilterMapInts], after the chunk counts of flt_tiles)
     // the exact paths' final re-scoring on large fp16 / fp32 shards (sketch.hip final_rescore_kernel): where the merge of an exact scan leaves its
     // rows before they are scored by the re-scoring arithmetic and re-ranked into the caller's arrays
     float* fin_scores = nullptr;   // [256][VQA_MAX_K_TOTAL]
@@ -576,7 +577,7 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
             hipMalloc((void**)&ix->thr_seed, VQA_QUERY_TILE * sizeof(float)) != hipSuccess ||
             hipMalloc((void**)&ix->upper, VQA_QUERY_TILE * sizeof(vqa_key)) != hipSuccess ||
             hipMalloc((void**)&ix->wide_flag, sizeof(int)) != hipSuccess ||
-            hipMalloc((void**)&ix->flt_tiles, ((size_t)tiles + 1 + vqa_filter_chunks(cap)) * sizeof(int)) != hipSuccess ||
+            hipMalloc((void**)&ix->flt_tiles, ((size_t)tiles + 1 + vqa_filter_chunks(cap) + kFilterMapInts) * sizeof(int)) != hipSuccess ||
             ((dtype == VQA_F16 || dtype == VQA_F32) &&
              (hipMalloc((void**)&ix->fin_scores, (size_t)VQA_QUERY_TILE * VQA_MAX_K_TOTAL * 4) != hipSuccess ||
               hipMalloc((void**)&ix->fin_ids, (size_t)VQA_QUERY_TILE * VQA_MAX_K_TOTAL * 8) != hipSuccess ||
@@ -585,6 +586,7 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
             rc = VQA_ENOMEM;
             break;
         }
+        ix->flt_qmap = ix->flt_tiles + tiles + 1 + vqa_filter_chunks(cap);
         ix->final_fma = o.final_rescore != 0;
         // int8 sketch: fp16 shards only, and only where a workgroup's tile maxima fit the scan's LDS
         // (and only for shards large enough for the two-stage search, whose main launch the sketch scan replaces)
@@ -689,7 +691,7 @@ extern "C" int vqa_index_create_ex(vqa_index** out, int device, int64_t n, int32
             (void)hipMemset(ix->thr0, byte, VQA_QUERY_TILE * sizeof(float));
             (void)hipMemset(ix->thr_seed, byte, VQA_QUERY_TILE * sizeof(float));
             (void)hipMemset(ix->upper, byte, VQA_QUERY_TILE * sizeof(vqa_key));
-            (void)hipMemset(ix->flt_tiles, byte, ((size_t)tiles + 1 + vqa_filter_chunks(cap)) * sizeof(int));
+            (void)hipMemset(ix->flt_tiles, byte, ((size_t)tiles + 1 + vqa_filter_chunks(cap) + kFilterMapInts) * sizeof(int));
             if (ix->sketch) {
                 (void)hipMemset(ix->qrow, byte, 5 * VQA_QUERY_TILE * sizeof(float));
                 (void)hipMemset(ix->qconst, byte, kSketchQRows * VQA_QUERY_TILE * sizeof(float));
@@ -1288,6 +1290,7 @@ extern "C" int vqa_index_search_host(vqa_index* ix, const void* q_host, int32_t 
 // One query tile of a call: queries [q0, q0 + nq) and their rows of the caller's outputs
 struct QueryTile {
     const void* q = nullptr;  // the tile's first query row
+    int q0 = 0;               // ... and its index in the call's batch
     int nq = 0;
     bool first = false, last = false;  // the call's first / last tile
     float* os = nullptr;
@@ -1307,6 +1310,7 @@ static int for_each_query_tile(const vqa_index* ix, const void* q, int32_t q_dty
     for (int q0 = 0; q0 < B; q0 += q_per) {
         QueryTile t;
         t.q = reinterpret_cast<const char*>(q) + (size_t)q0 * q_row;
+        t.q0 = q0;
         t.nq = B - q0 < q_per ? B - q0 : q_per;
         t.first = q0 == 0;
         t.last = q0 + q_per >= B;
@@ -1602,25 +1606,38 @@ static int search_impl(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B,
 // captured graph replays any selection.  The sketch is never used and its pause state is neither read nor changed: the bound speaks of
 // all rows, not of a selection.  Where the exact paths end in the re-scoring arithmetic (final_rescore_applies) this one does too, the
 // same way, so an all-ones bitmap returns the bits of vqa_index_search on the handle.
-static int filtered_impl(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B, int32_t k, const uint32_t* allow, float* out_scores,
-                         int64_t* out_ids, int64_t* out_pos_or_null, hipStream_t stream) {
+// One bitmap per query (vqa_index_search_filtered_multi, query_filter not null): the compaction moves into the query tile -- the union
+// of the bitmaps its queries use, and the tile's query map -- and the passes are MODE 4 launches, which mask per (row, query).
+static int filtered_impl(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B, int32_t k, const uint32_t* allow, const int32_t* query_filter,
+                         int32_t F, float* out_scores, int64_t* out_ids, int64_t* out_pos_or_null, hipStream_t stream) {
     const LaunchPlan p = plan_launch(ix, k);
     int* const list = ix->flt_tiles;
     int* const count = ix->flt_tiles + p.tiles;
     int rc = VQA_OK;
-    if (ix->n > 0 && (rc = vqa_launch_filter_tiles(allow, ix->n, list, count, count + 1, stream)) != VQA_OK) return rc;
+    if (!query_filter && ix->n > 0 && (rc = vqa_launch_filter_tiles(allow, ix->n, list, count, count + 1, stream)) != VQA_OK) return rc;
     FilterScanArgs f;
     f.tiles = list;
     f.count = count;
     f.allow = allow;
     f.nwords = (ix->n + 31) / 32;
+    f.qmap = query_filter ? ix->flt_qmap : nullptr;
     ExactPasses x;  // no seed pass, one stage
     x.filter = &f;
     return for_each_query_tile(ix, q, q_dtype, B, k, out_scores, out_ids, out_pos_or_null, [&](const QueryTile& t) {
         if (ix->n == 0) return pad_empty_shard(ix, t, k, stream);
+        if (query_filter && (rc = vqa_launch_filter_tiles_multi(allow, ix->n, query_filter + t.q0, t.nq, F, list, count, count + 1, ix->flt_qmap,
+                                                                stream)) != VQA_OK)
+            return rc;
         if ((rc = stage_query_tile(ix, t, q_dtype, false, stream)) != VQA_OK) return rc;
         return exact_passes(ix, p, t, k, x, stream);
     });
+}
+
+static bool is_device_pointer(const void* ptr) {
+    hipPointerAttribute_t attr;
+    const bool device = hipPointerGetAttributes(&attr, ptr) == hipSuccess && attr.type == hipMemoryTypeDevice;
+    if (!device) (void)hipGetLastError();
+    return device;
 }
 
 extern "C" int vqa_index_search_filtered(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B, int32_t k, const uint32_t* allow_bits,
@@ -1631,16 +1648,29 @@ extern "C" int vqa_index_search_filtered(vqa_index* ix, const void* q, int32_t q
     VQA_REQUIRE(B >= 1, "vqa_index_search_filtered: B=%d", B);
     VQA_REQUIRE(k >= 1 && k <= VQA_MAX_K_TOTAL, "vqa_index_search_filtered: k=%d outside [1, %d]", k, VQA_MAX_K_TOTAL);
     VQA_REQUIRE(q_dtype == VQA_F32 || q_dtype == VQA_F16, "vqa_index_search_filtered: q_dtype %d is not f32/f16", q_dtype);
-    {
-        hipPointerAttribute_t attr;
-        const bool device = hipPointerGetAttributes(&attr, allow_bits) == hipSuccess && attr.type == hipMemoryTypeDevice;
-        if (!device) (void)hipGetLastError();
-        VQA_REQUIRE(device, "vqa_index_search_filtered: allow_bits is not device memory");
-    }
+    VQA_REQUIRE(is_device_pointer(allow_bits), "vqa_index_search_filtered: allow_bits is not device memory");
     HandleBusy busy(ix->busy);
     VQA_REQUIRE(busy.ok, "vqa_index_search_filtered: this index handle is in use by another host thread (one call at a time per handle)");
     DeviceGuard guard(ix->device);
-    return filtered_impl(ix, q, q_dtype, B, k, allow_bits, out_scores, out_ids, out_pos_or_null, (hipStream_t)hip_stream);
+    return filtered_impl(ix, q, q_dtype, B, k, allow_bits, nullptr, 0, out_scores, out_ids, out_pos_or_null, (hipStream_t)hip_stream);
+}
+
+extern "C" int vqa_index_search_filtered_multi(vqa_index* ix, const void* q, int32_t q_dtype, int32_t B, int32_t k, const uint32_t* allow_bits,
+                                               int32_t F, const int32_t* query_filter, float* out_scores, int64_t* out_ids,
+                                               int64_t* out_pos_or_null, void* hip_stream) {
+    VQA_REQUIRE(ix, "vqa_index_search_filtered_multi: index is null");
+    VQA_REQUIRE(q && out_scores && out_ids, "vqa_index_search_filtered_multi: null pointer");
+    VQA_REQUIRE(allow_bits && query_filter, "vqa_index_search_filtered_multi: allow_bits / query_filter is null");
+    VQA_REQUIRE(F >= 1, "vqa_index_search_filtered_multi: F=%d", F);
+    VQA_REQUIRE(B >= 1, "vqa_index_search_filtered_multi: B=%d", B);
+    VQA_REQUIRE(k >= 1 && k <= VQA_MAX_K_TOTAL, "vqa_index_search_filtered_multi: k=%d outside [1, %d]", k, VQA_MAX_K_TOTAL);
+    VQA_REQUIRE(q_dtype == VQA_F32 || q_dtype == VQA_F16, "vqa_index_search_filtered_multi: q_dtype %d is not f32/f16", q_dtype);
+    VQA_REQUIRE(is_device_pointer(allow_bits), "vqa_index_search_filtered_multi: allow_bits is not device memory");
+    VQA_REQUIRE(is_device_pointer(query_filter), "vqa_index_search_filtered_multi: query_filter is not device memory");
+    HandleBusy busy(ix->busy);
+    VQA_REQUIRE(busy.ok, "vqa_index_search_filtered_multi: this index handle is in use by another host thread (one call at a time per handle)");
+    DeviceGuard guard(ix->device);
+    return filtered_impl(ix, q, q_dtype, B, k, allow_bits, query_filter, F, out_scores, out_ids, out_pos_or_null, (hipStream_t)hip_stream);
 }
 
 // ---- diagnostics of the sketch search (bench.py prices a step's physical bytes from the pair counts; tests/test_gpu_sketch_bound.py

@@ -26,6 +26,8 @@
 //   a kernel trace keeps it apart from the main launch.)
 //   MODE 3 "filtered": MODE 1 over the tiles of a device-resident list (filter.hip), rows whose bit is clear in the caller's bitmap
 //                  masked out before the threshold test (vqa_index_search_filtered, capi.hip).
+//   MODE 4 "filtered, per query": MODE 3 over the union of a query tile's bitmaps; accumulator (row, query) masked out when the bit is
+//                  clear in that query's own bitmap (vqa_index_search_filtered_multi, capi.hip).
 #include <type_traits>
 #include <utility>
 
@@ -243,6 +245,28 @@ __device__ __forceinline__ uint32_t sload_u32(const void* base, uint32_t idx) {
     return v;
 }
 
+// MODE 4: four consecutive words at a workgroup-uniform, dword-aligned address by one scalar load (SMEM needs no more alignment)
+__device__ __forceinline__ void sload_u32x4(const uint32_t* p, uint32_t (&w)[4]) {
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4s;
+    u32x4s v;
+    asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
+    w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+}
+
+// ... and four such loads in flight at once, one wait (the words of four queries)
+__device__ __forceinline__ void sload_4x_u32x4(const uint32_t* p0, const uint32_t* p1, const uint32_t* p2, const uint32_t* p3,
+                                               uint32_t (&w)[4][4]) {
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4s;
+    u32x4s a, b, c, d;
+    asm volatile("s_load_dwordx4 %0, %4, 0x0\n\ts_load_dwordx4 %1, %5, 0x0\n\ts_load_dwordx4 %2, %6, 0x0\n\ts_load_dwordx4 %3, %7, 0x0\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(a), "=&s"(b), "=&s"(c), "=&s"(d) : "s"(p0), "s"(p1), "s"(p2), "s"(p3) : "memory");
+    w[0][0] = a.x, w[0][1] = a.y, w[0][2] = a.z, w[0][3] = a.w;
+    w[1][0] = b.x, w[1][1] = b.y, w[1][2] = b.z, w[1][3] = b.w;
+    w[2][0] = c.x, w[2][1] = c.y, w[2][2] = c.z, w[2][3] = c.w;
+    w[3][0] = d.x, w[3][1] = d.y, w[3][2] = d.z, w[3][3] = d.w;
+}
+
 __device__ __forceinline__ bool append_candidate(const Lists& L, int q, float v, uint32_t pos, int spill) {
     const int slot = atomicAdd(&L.cnt[q], 1) & kCntMask;  // ds_add_rtn_u32
     if (slot < kCap) {
@@ -415,7 +439,8 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
     const int c = lane & 15;
     const int g = lane >> 4;
 
-    constexpr bool kLists = MODE == 1 || MODE == 3;  // candidate lists in LDS, flushed for K2
+    constexpr bool kLists = MODE == 1 || MODE == 3 || MODE == 4;  // candidate lists in LDS, flushed for K2
+    constexpr bool kListed = MODE == 3 || MODE == 4;                 // tiles from a device list (filter.hip)
     if (kLists && tid < kQ) {
         L.thr[tid] = tid < nq ? (thr_init ? thr_init[tid] : -INFINITY) : INFINITY;
         L.cnt[tid] = 0;
@@ -449,7 +474,7 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
     };
     int first_tile = tile_begin + blockIdx.x;
     int ntile = first_tile < tile_end ? (tile_end - first_tile + (int)gridDim.x - 1) / (int)gridDim.x : 0;
-    if constexpr (MODE == 3) {
+    if constexpr (kListed) {
         flt = __builtin_bit_cast(FilterScanArgs, sk);
         const int list_n = (int)sload_u32(flt.count, 0);
         first_tile = (int)blockIdx.x < list_n ? tile_at(0) : 0;
@@ -488,7 +513,7 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
         x_src += kOperandBytes;
         if (++i_kt == KT) {
             i_kt = 0;
-            if constexpr (MODE == 3) {
+            if constexpr (kListed) {
                 if (ik < total) x_src = reinterpret_cast<const char*>(X) + (size_t)tile_at(ik / KT) * KT * kOperandBytes;
             } else {
                 x_src += tile_jump;
@@ -658,6 +683,76 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
                 const bool dead = !((nib >> j) & 1u);
 #pragma unroll
                 for (int ni = 0; ni < 4; ++ni) acc[mi][ni][j] = dead ? __builtin_nanf("") : acc[mi][ni][j];
+            }
+        }
+    };
+    // MODE 4: as MODE 3, but query q = wn * 64 + ni * 16 + c (lane c of column group ni) takes words 4 wm .. 4 wm + 3 of the tile from
+    // its own bitmap flt.allow + qmap[q] * nwords.  Every load is scalar, for the same reason as in MODE 3: a per-lane global load here
+    // would make hipcc drain the LDS-DMA ring.  A 16-query group whose live queries share one bitmap (qmap[256 + group]: a tenant, a
+    // shared filter) loads it once; a mixed group loads each query's 4 words and lane c keeps query c's.
+    [[maybe_unused]] auto mask_per_query = [&](f32x4 (&acc)[8][4], uint32_t row0) __attribute__((always_inline)) {
+        const long long w0 = (long long)(row0 >> 5) + 4 * wm;
+        const bool whole = w0 + 4 <= flt.nwords;  // only the shard's last tile reads fewer (and the rows past n are NaN already)
+        auto words_of = [&](int e, uint32_t (&w)[4]) __attribute__((always_inline)) {
+            if (e == kFilterAll) {
+                w[0] = w[1] = w[2] = w[3] = 0xFFFFFFFFu;
+            } else if (e < 0) {
+                w[0] = w[1] = w[2] = w[3] = 0u;
+            } else {
+                const uint32_t* base = flt.allow + (size_t)e * (size_t)flt.nwords;
+                if (whole) {
+                    sload_u32x4(base + w0, w);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) w[i] = w0 + i < flt.nwords ? sload_u32(base, (uint32_t)(w0 + i)) : 0u;
+                }
+            }
+        };
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+            const int qg = wn * 64 + ni * 16;
+            const int common = (int)sload_u32(flt.qmap, (uint32_t)(VQA_QUERY_TILE + qg / 16));
+            uint32_t w[4];
+            if (common != kFilterMixed) {
+                words_of(common, w);
+            } else if (whole) {
+                // four queries at a time: their entries by one scalar load, their words by four loads in flight (an entry that names
+                // no bitmap loads bitmap 0's words, valid memory, and replaces them)
+                w[0] = w[1] = w[2] = w[3] = 0u;
+#pragma nounroll
+                for (int c4 = 0; c4 < 16; c4 += 4) {  // (rolled: four bodies of scalar loads spill the kernel's SGPRs)
+                    uint32_t e[4], s4[4][4];
+                    sload_u32x4(reinterpret_cast<const uint32_t*>(flt.qmap) + qg + c4, e);
+                    const uint32_t* p[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) p[i] = flt.allow + (size_t)((int)e[i] >= 0 ? e[i] : 0u) * (size_t)flt.nwords + w0;
+                    sload_4x_u32x4(p[0], p[1], p[2], p[3], s4);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int ei = (int)e[i];
+#pragma unroll
+                        for (int x = 0; x < 4; ++x) {
+                            const uint32_t v = ei >= 0 ? s4[i][x] : ei == kFilterAll ? 0xFFFFFFFFu : 0u;
+                            w[x] = c == c4 + i ? v : w[x];
+                        }
+                    }
+                }
+            } else {  // the shard's last tile: word by word, none at or past nwords
+                w[0] = w[1] = w[2] = w[3] = 0u;
+#pragma nounroll
+                for (int cc = 0; cc < 16; ++cc) {
+                    uint32_t s4[4];
+                    words_of((int)sload_u32(flt.qmap, (uint32_t)(qg + cc)), s4);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) w[i] = c == cc ? s4[i] : w[i];
+                }
+            }
+#pragma unroll
+            for (int mi = 0; mi < 8; ++mi) {
+                const uint32_t nib = w[mi >> 1] >> ((mi & 1) * 16 + g * 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (!((nib >> j) & 1u)) acc[mi][ni][j] = __builtin_nanf("");
             }
         }
     };
@@ -858,13 +953,14 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
     // `ext_stage`: an X ring stage that stays idle until every wave has passed the next workgroup barrier
     auto finish_tile = [&](f32x4 (&acc)[8][4], int ti, int ext_stage) __attribute__((always_inline)) {
         uint32_t row0 = ((uint32_t)first_tile + (uint32_t)ti * gridDim.x) * kTileRows;  // n < 2^32 rows
-        if constexpr (MODE == 3) row0 = (uint32_t)tile_at(ti) * kTileRows;
+        if constexpr (kListed) row0 = (uint32_t)tile_at(ti) * kTileRows;
         if (MODE == 2) {
             sketch_epilogue(acc, row0, ti);
             return;
         }
         mask_ragged(acc, row0);
         if constexpr (MODE == 3) mask_filter(acc, row0);
+        if constexpr (MODE == 4) mask_per_query(acc, row0);
         if (MODE == 0) {
             seed_epilogue(acc, row0, ti);
             return;
@@ -1009,7 +1105,7 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
                 if (++src_kt == KT) {
                     src_kt = 0;
                     if constexpr (kQ0) src = reinterpret_cast<const char*>(Qs);
-                    else if constexpr (MODE == 3) src = reinterpret_cast<const char*>(X) + (size_t)tile_at(n_issued / KT) * KT * kOperandBytes;
+                    else if constexpr (kListed) src = reinterpret_cast<const char*>(X) + (size_t)tile_at(n_issued / KT) * KT * kOperandBytes;
                     else src += tile_jump;
                 }
             }
@@ -1218,7 +1314,7 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
             x_kt += 2;
             if (x_kt >= KT) {
                 x_kt -= KT;
-                if constexpr (MODE == 3) {
+                if constexpr (kListed) {
                     if (xk < total) xs = reinterpret_cast<const char*>(X) + ((size_t)tile_at(xk / KT) * KT + x_kt) * kOperandBytes;
                 } else {
                     xs += tile_jump;
@@ -1300,10 +1396,11 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
                 if (kLists && !kEarly && jj == P - 1) repair(false, fq_other);  // group A's E slot just ended
             }
             // ---- E slot
-            if constexpr (MODE == 3) row0 = (uint32_t)tile_at(ti) * kTileRows;
+            if constexpr (kListed) row0 = (uint32_t)tile_at(ti) * kTileRows;
             else row0 = ((uint32_t)first_tile + (uint32_t)ti * gridDim.x) * kTileRows;
             mask_ragged(acc, row0);
             if constexpr (MODE == 3) mask_filter(acc, row0);
+            if constexpr (MODE == 4) mask_per_query(acc, row0);
             if (MODE == 0) {
                 seed_epilogue(acc, row0, ti);
                 block_barrier();
@@ -1319,8 +1416,8 @@ __global__ __launch_bounds__(kThreads) void score_topk_kernel(const void* __rest
         }
     };
 
-    // MODE 3: a workgroup whose share of the list is empty issues no load at all (not even the ring's prologue); its lists flush empty
-    if (MODE != 3 || ntile > 0) {
+    // MODE 3 / 4: a workgroup whose share of the list is empty issues no load at all (not even the ring's prologue); its lists flush empty
+    if (!kListed || ntile > 0) {
     if constexpr (kStagger) {
         if (grp) stagger_loop(std::false_type{});
         else stagger_loop(std::true_type{});
@@ -1428,17 +1525,20 @@ static int launch_sketch(const ScoreTopkArgs& a, int KT, int lds, hipStream_t st
 
 int vqa_score_topk_sketch_max_tiles() { return kSketchMaxTiles; }
 
-// MODE 3: the filtered scan over the tiles of a device list (fp16 on the slot loop, fp8 on the stagger loop, fp32 on the tile loop)
+// MODE 3 / 4: the filtered scan over the tiles of a device list (fp16 on the slot loop, fp8 on the stagger loop, fp32 on the tile loop)
 template <int DT>
 static int launch_filtered(const ScoreTopkArgs& a, int KT, int lds, hipStream_t stream) {
     static VqaPerDeviceOnce once;
     int rc = once.run([&](int) -> int {
         VQA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(score_topk_kernel<3, DT, 0, 0>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        VQA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(score_topk_kernel<4, DT, 0, 0>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         return VQA_OK;
     });
     if (rc != VQA_OK) return rc;
-    hipLaunchKernelGGL((score_topk_kernel<3, DT, 0, 0>), dim3(a.grid), dim3(kThreads), lds, stream, a.x, a.q, a.thr_init, a.upper, a.partial,
+    // MODE 4 when the filter carries a query map (one bitmap per query)
+    hipLaunchKernelGGL((a.filter->qmap ? score_topk_kernel<4, DT, 0, 0> : score_topk_kernel<3, DT, 0, 0>), dim3(a.grid), dim3(kThreads), lds, stream, a.x, a.q, a.thr_init, a.upper, a.partial,
                        (long long)a.n, KT, a.nq, a.k, 0, 0, nullptr, a.row_lists > 0 ? a.row_lists : a.grid, a.list_offset, 2,
                        vqa_filter_carrier(*a.filter));
     VQA_HIP_CHECK(hipGetLastError());

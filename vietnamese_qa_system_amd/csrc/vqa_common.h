@@ -156,8 +156,14 @@ struct FilterScanArgs {
     const int* count = nullptr;      // ... and how many there are (device: the host never learns it)
     const uint32_t* allow = nullptr; // [nwords] the caller's row bitmap, bit p & 31 of word p >> 5
     long long nwords = 0;            // ceil(n / 32): no word at or past it is read
-    unsigned char unused[32] = {};
+    // MODE 4 (one bitmap per query, vqa_index_search_filtered_multi): `allow` is [F][nwords] and qmap the query tile's map that
+    // vqa_launch_filter_tiles_multi wrote: [256] bitmap of each query (kFilterAll / kFilterNone), then [16] per 16-query group the
+    // bitmap every live query of the group shares, or kFilterMixed.  nullptr: MODE 3.
+    const int* qmap = nullptr;
+    unsigned char unused[24] = {};
 };
+constexpr int kFilterAll = -1, kFilterNone = -2, kFilterMixed = -3;
+constexpr int kFilterMapInts = VQA_QUERY_TILE + VQA_QUERY_TILE / 16;
 
 // ---- kernel launchers implemented in the .hip files ---------------------------------------------------------
 struct ScoreTopkArgs {
@@ -184,7 +190,7 @@ struct ScoreTopkArgs {
     bool seed_only = false;  // MODE 0: writes seeds_per_tile sub-maxima per query and tile to `partial` as [query][tile - tile_begin][.]
     int32_t seeds_per_tile = 2;  // 2 (one per 128-row half) or 8 (one per 32-row group: shards of a few tiles, where 2 per tile
                                  // are fewer than k values and leave the thresholds at -inf)
-    const FilterScanArgs* filter = nullptr;  // not null: MODE 3 over the listed tiles (tile_begin / tile_end unused; grid <= tiles of the shard)
+    const FilterScanArgs* filter = nullptr;  // not null: MODE 3 (MODE 4 with filter->qmap) over the listed tiles (tile_begin / tile_end unused; grid <= tiles of the shard)
 };
 static_assert(sizeof(FilterScanArgs) == sizeof(SketchScanArgs), "MODE 3 carries its arguments in the bytes of SketchScanArgs");
 __host__ __device__ inline SketchScanArgs vqa_filter_carrier(const FilterScanArgs& f) { return __builtin_bit_cast(SketchScanArgs, f); }
@@ -192,6 +198,10 @@ __host__ __device__ inline SketchScanArgs vqa_filter_carrier(const FilterScanArg
 // (two launches; `chunk_cnt`: vqa_filter_chunks(n) ints of scratch)
 int vqa_filter_chunks(int64_t n);
 int vqa_launch_filter_tiles(const uint32_t* allow, int64_t n, int* tiles, int* count, int* chunk_cnt, hipStream_t stream);
+// ... and the union of the bitmaps the nq queries of one query tile use (query_filter: [nq] entries, f in [0, F), -1 all rows, else
+// none), plus the tile's query map for MODE 4 (qmap: kFilterMapInts ints)
+int vqa_launch_filter_tiles_multi(const uint32_t* allow, int64_t n, const int* query_filter, int nq, int F, int* tiles, int* count,
+                                  int* chunk_cnt, int* qmap, hipStream_t stream);
 int vqa_launch_score_topk(int dtype, const ScoreTopkArgs& a, hipStream_t stream);
 // scan_regq.hip: the sketch scan with the query operand resident in registers (rows of 768 / 384 one-byte elements, no per-row betas)
 bool vqa_sketch_regq_applies(const ScoreTopkArgs& a);

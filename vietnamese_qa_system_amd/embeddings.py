@@ -34,7 +34,7 @@ import torch.distributed as dist
 from . import _native as N
 from . import docstore
 from .index import _STORE_NP, DeviceIndex, compaction_moves, resolve_dtype
-from .rowfilter import RowFilter
+from .rowfilter import RowFilter, RowFilterBatch
 from .sharded import ShardedSearcher, shard_bounds
 from .sparse import BM25Index, combine
 
@@ -99,7 +99,7 @@ class Embeddings:
         self._docs_rows: Optional[list] = None  # [(device-level id, document)] of the rows this rank was given
         self._lo = 0                            # first global row of this rank's shard
         self._shard_ids: Optional[np.ndarray] = None  # host copy of this shard's id vector (filters by id / by document field)
-        self._allow: Optional[RowFilter] = None  # the shard's filter of the search in progress (_local_search)
+        self._allow = None  # the shard's RowFilter / RowFilterBatch of the search in progress (_local_search)
         self.load_stats: Optional[dict] = None  # filled by load(): bytes, seconds, GB/s of the file -> HBM stream
         self._mutable = False                   # upsert / delete happened: the shard carries an id vector of stable integer keys
         self._docs_over: Optional[dict] = None  # loaded index: key -> upserted document (None: deleted) over documents.db
@@ -633,16 +633,72 @@ class Embeddings:
             v = out
         return v
 
-    def batchsearch(self, queries, limit: int = 3, filter=None) -> List[list]:
+    @staticmethod
+    def _filter_key(flt):
+        """What makes two entries of ``filters=`` the same filter: a RowFilter by identity, a dict by its normalised items, ids by value."""
+        if isinstance(flt, RowFilter):
+            return ("rowfilter", id(flt))
+        if isinstance(flt, dict):
+            def norm(v):
+                vals = list(v) if isinstance(v, (list, tuple, set, frozenset)) else [v]
+                return tuple(sorted(set(vals), key=repr))
+            return ("fields", tuple(sorted((str(k), norm(v)) for k, v in flt.items())))
+        vals = flt.tolist() if isinstance(flt, (np.ndarray, torch.Tensor)) else list(flt)
+        return ("ids", tuple(vals))
+
+    def _filtered_multi(self, queries, limit: int, filters) -> List[list]:
+        """batchsearch with one filter per query: each distinct filter resolved once, then ONE filtered search of the whole batch
+        (vqa_index_search_filtered_multi on every rank, the same all-gather and merge), one sync."""
+        q = self._query_vectors(queries)
+        if q.shape[1] != self.d:
+            raise ValueError(f"query dimension {q.shape[1]} != index dimension {self.d}")
+        texts = list(queries) if not isinstance(queries, (np.ndarray, torch.Tensor)) and len(queries) and isinstance(queries[0], str) else None
+        hybrid = self.hybrid and self._sparse is not None and texts is not None and 0.0 < self.weights < 1.0
+        resolved = {}
+        locals_, globs = [], []
+        for flt in filters:
+            if flt is None:
+                locals_.append(None)
+                globs.append(None)
+                continue
+            key = self._filter_key(flt)
+            if key not in resolved:
+                resolved[key] = self._resolve_filter(flt, need_global=hybrid)
+            local, glob = resolved[key]
+            locals_.append(local)
+            globs.append(glob)
+        batch = RowFilterBatch(locals_)
+        if hybrid:
+            return self._hybrid(q, texts, limit, allow=(batch, globs))
+        self._allow = batch
+        try:
+            scores, ids = self._searcher.search(q, limit)
+        finally:
+            self._allow = None
+        torch.cuda.current_stream(q.device).synchronize()
+        return self._format(scores.cpu().numpy(), ids.cpu().numpy())
+
+    def batchsearch(self, queries, limit: int = 3, filter=None, *, filters=None) -> List[list]:
         """txtai ``batchsearch``: one result list per query; ``queries`` is a list of strings or a [B, d] array.  ``filter``: search
         only part of the corpus -- an iterable of ids, a ``{field: value(s)}`` dict matched against the stored documents (e.g.
         ``{"source": "x"}``), or a :class:`RowFilter` over the corpus' row positions; the result is the exact top ``limit`` among
-        those rows (fewer only when fewer are selected)."""
+        those rows (fewer only when fewer are selected).  ``filters``: one filter per query instead (a list of B entries, each
+        anything ``filter`` accepts, or None for the whole corpus), searched as one batch; equal entries are resolved once."""
         if self._index is None:
             raise RuntimeError("the index is empty: call index()/load() first")
         if isinstance(queries, str):
             queries = [queries]
         limit = int(limit)
+        if filters is not None:
+            if filter is not None:
+                raise ValueError("pass either filter= (one filter for the batch) or filters= (one per query), not both")
+            if isinstance(filters, (str, dict, RowFilter)) or not hasattr(filters, "__len__"):
+                raise ValueError("filters= takes a list with one entry per query")
+            if len(filters) != len(queries):
+                raise ValueError(f"filters= has {len(filters)} entries for {len(queries)} queries (one per query, None for no filter)")
+            if isinstance(queries, np.ndarray) and queries.dtype == np.float64:
+                queries = queries.astype(np.float32)
+            return self._filtered_multi(queries, limit, list(filters))
         if filter is not None:
             if isinstance(queries, np.ndarray) and queries.dtype == np.float64:
                 queries = queries.astype(np.float32)
@@ -771,7 +827,8 @@ class Embeddings:
             sparse_all = [[(int(self._row_ids[r]), s) for r, s in self._sparse.search(text, cand)] for text in texts]
             ds, di = self._index.search_host(q, cand, normalize=self.normalize)
         else:
-            # a filter (allow = (this shard's RowFilter, global row mask)) restricts both halves before their top-`cand` cuts
+            # a filter (allow = (this shard's RowFilter, global row mask) or (RowFilterBatch, a mask or None per query)) restricts both
+            # halves before their top-`cand` cuts
             self._allow = allow[0] if allow is not None else None
             try:
                 scores, ids = self._searcher.search(q, cand)
@@ -783,8 +840,11 @@ class Embeddings:
         out_i = np.full((len(texts), limit), -1, dtype=np.int64)
         for b, text in enumerate(texts):
             dense = [(int(i), float(s)) for i, s in zip(di[b], ds[b]) if i >= 0 and s > 0]  # txtai drops dense scores <= 0
+            mask = allow[1] if allow is not None else None
+            if isinstance(mask, list):  # one filter per query (filters=)
+                mask = mask[b]
             sparse = sparse_all[b] if sparse_all is not None else [
-                (int(self._row_ids[r]), s) for r, s in self._sparse.search(text, cand, allow=allow[1] if allow is not None else None)]
+                (int(self._row_ids[r]), s) for r, s in self._sparse.search(text, cand, allow=mask)]
             for j, (uid, sc) in enumerate(combine(dense, sparse, limit, self.weights, self._sparse.normalize)):
                 out_i[b, j], out_s[b, j] = uid, sc
         return self._format(out_s, out_i)

@@ -7,13 +7,13 @@ runs in ``libvqa_retrieval.so`` (hand-written HIP, gfx950); torch only owns devi
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
 from . import _native as N
-from .rowfilter import RowFilter
+from .rowfilter import RowFilter, RowFilterBatch
 
 RESCORE_COPY_MAX_BYTES = 32 << 30  # rows of up to 32 GiB get the row-major re-scoring copy by default (DeviceIndex)
 _SRC_DTYPE = {torch.float32: N.VQA_F32, torch.float16: N.VQA_F16}
@@ -285,13 +285,16 @@ class DeviceIndex:
         return flt
 
     def search(self, queries: torch.Tensor, k: int, *, return_positions: bool = False,
-               out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, allow: Optional[RowFilter] = None
+               out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+               allow: Union[RowFilter, RowFilterBatch, Sequence[Optional[RowFilter]], None] = None
                ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
         """``queries`` [B, d] fp32/fp16 cuda tensor -> (scores [B, k] fp32, ids [B, k] int64[, positions]), best first,
         ties by row position; slots beyond the shard's row count hold (-inf, -1).  Asynchronous on the current stream.
         ``out`` = (scores, ids): contiguous [B, k] float32 / int64 tensors on this device to write into (the sharded
         searcher passes views of its all-gather send buffer).  ``allow``: a :class:`RowFilter` of this shard (:meth:`row_filter`):
-        the exact top-k among its rows only (``vqa_index_search_filtered``), padded with (-inf, -1) past the rows it allows."""
+        the exact top-k among its rows only (``vqa_index_search_filtered``), padded with (-inf, -1) past the rows it allows.
+        ``allow`` may also give every query its own filter: a :class:`RowFilterBatch` of B entries, or a list of B ``RowFilter |
+        None`` (None: all rows), searched in one call (``vqa_index_search_filtered_multi``)."""
         if not self._handle.value:
             raise RuntimeError("index is closed")
         dev = torch.device("cuda", self.device)
@@ -308,8 +311,24 @@ class DeviceIndex:
             for t, dt in ((scores, torch.float32), (ids, torch.int64)):
                 if t.dtype != dt or tuple(t.shape) != (b, k) or t.device != dev or not t.is_contiguous():
                     raise ValueError(f"out tensors must be contiguous [{b}, {k}] float32 / int64 on {dev}")
-        if allow is not None:
-            if not isinstance(allow, RowFilter) or allow.n != self.n:
+        if allow is not None and not isinstance(allow, (RowFilter, RowFilterBatch)):
+            allow = RowFilterBatch(allow)
+        if isinstance(allow, RowFilterBatch):
+            if len(allow) != b:
+                raise ValueError(f"the RowFilterBatch has {len(allow)} entries for {b} queries")
+            if allow.generation is not None and allow.generation != self.generation:
+                raise ValueError(f"the RowFilterBatch was built at generation {allow.generation} of this shard, which has changed since "
+                                 f"(generation {self.generation}): build its filters again with row_filter()")
+            if allow.n is not None and allow.n != self.n:
+                raise ValueError(f"allow must be a RowFilterBatch of this shard's {self.n} rows (it has {allow.n})")
+            if allow.n is None:  # every query searches all rows
+                allow = allow.to(dev)
+            elif allow.bits.device != dev:
+                raise ValueError(f"the RowFilterBatch lives on {allow.bits.device}, the shard on {dev}: build it with row_filter()")
+            # the library wants F >= 1 device bitmaps: an empty shard's (or an all-None batch's) are one unused word each
+            mbits = allow.bits if allow.n is not None and allow.bits.numel() else torch.zeros((allow.F, 1), dtype=torch.int32, device=dev)
+        elif allow is not None:
+            if allow.n != self.n:
                 raise ValueError(f"allow must be a RowFilter of this shard's {self.n} rows")
             if allow.generation is not None and allow.generation != self.generation:
                 raise ValueError(f"the RowFilter was built at generation {allow.generation} of this shard, which has changed since "
@@ -322,7 +341,11 @@ class DeviceIndex:
                 ids = torch.empty((b, k), dtype=torch.int64, device=dev)
             pos = torch.empty((b, k), dtype=torch.int64, device=dev) if return_positions else None
             stream = torch.cuda.current_stream(dev).cuda_stream
-            if allow is not None:
+            if isinstance(allow, RowFilterBatch):
+                N.check(self._lib.vqa_index_search_filtered_multi(
+                    self._handle, q.data_ptr(), _SRC_DTYPE[q.dtype], b, int(k), mbits.data_ptr(), allow.F, allow.query_filter.data_ptr(),
+                    scores.data_ptr(), ids.data_ptr(), pos.data_ptr() if pos is not None else None, stream), "vqa_index_search_filtered_multi")
+            elif allow is not None:
                 N.check(self._lib.vqa_index_search_filtered(self._handle, q.data_ptr(), _SRC_DTYPE[q.dtype], b, int(k), allow.bits.data_ptr(),
                                                             scores.data_ptr(), ids.data_ptr(), pos.data_ptr() if pos is not None else None,
                                                             stream), "vqa_index_search_filtered")

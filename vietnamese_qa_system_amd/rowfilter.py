@@ -1,4 +1,5 @@
-"""Row filters of a filtered search (``vqa_index_search_filtered``): one bit per row position of a shard.
+"""Row filters of a filtered search (``vqa_index_search_filtered``): one bit per row position of a shard.  A
+:class:`RowFilterBatch` gives each query of a batch its own filter (``vqa_index_search_filtered_multi``).
 
 Layout (include/vqa_retrieval.h): ``ceil(n / 32)`` 32-bit words, row position ``p`` allowed iff
 ``(bits[p >> 5] >> (p & 31)) & 1``; bits at positions >= n are ignored by the library.  A :class:`RowFilter` holds the words
@@ -8,7 +9,7 @@ bytes.  Nothing here needs a GPU; :meth:`DeviceIndex.row_filter` builds one on t
 """
 from __future__ import annotations
 
-from typing import Optional, Union
+from typing import List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -104,3 +105,76 @@ class RowFilter:
 
     def __repr__(self) -> str:
         return f"RowFilter(n={self.n}, allowed={self.allowed}, tiles={self.tiles}, device={self.bits.device})"
+
+
+class RowFilterBatch:
+    """One filter per query of a batch of B (``vqa_index_search_filtered_multi``): the distinct filters stacked as int32
+    ``bits [F, ceil(n / 32)]`` and ``query_filter`` int32 ``[B]``, the filter of each query (``-1``: all rows).  Built from a
+    list of B ``RowFilter | None``; a filter object that appears several times is stored once (by identity).  Reusable across
+    searches and graph captures, like a :class:`RowFilter`; ``generation`` is the shard generation every filter was built at."""
+
+    def __init__(self, filters: Sequence[Optional[RowFilter]]):
+        filters = list(filters)
+        if not filters:
+            raise ValueError("a RowFilterBatch needs one entry per query (got none)")
+        distinct: List[RowFilter] = []
+        index = {}
+        assign = []
+        for f in filters:
+            if f is None:
+                assign.append(-1)
+                continue
+            if not isinstance(f, RowFilter):
+                raise ValueError(f"RowFilterBatch entries must be RowFilter or None, got {type(f).__name__}")
+            if id(f) not in index:
+                index[id(f)] = len(distinct)
+                distinct.append(f)
+            assign.append(index[id(f)])
+        ns = {f.n for f in distinct}
+        devs = {f.bits.device for f in distinct}
+        gens = {f.generation for f in distinct if f.generation is not None}  # (a filter built from a mask has none)
+        if len(ns) > 1 or len(devs) > 1:
+            raise ValueError("the filters of a RowFilterBatch must all be of one shard (same n, same device)")
+        if len(gens) > 1:
+            raise ValueError(f"the filters of a RowFilterBatch were built at different shard generations {sorted(map(str, gens))}")
+        self.filters = distinct
+        self.n = distinct[0].n if distinct else None  # None: every query searches all rows (fits any shard)
+        self.generation = gens.pop() if gens else None
+        dev = distinct[0].bits.device if distinct else torch.device("cpu")
+        nw = (self.n + 31) // 32 if distinct else 0
+        # F >= 1 always (the library requires it): an all -1 batch carries one empty bitmap nobody uses
+        self.bits = (torch.stack([f.bits for f in distinct]) if distinct
+                     else torch.zeros((1, nw), dtype=torch.int32, device=dev)).contiguous()
+        self.query_filter = torch.tensor(assign, dtype=torch.int32).to(dev)
+        self.assign = assign
+
+    def __len__(self) -> int:
+        return len(self.assign)
+
+    @property
+    def F(self) -> int:
+        return int(self.bits.shape[0])
+
+    def _with(self, filters: List[RowFilter]) -> "RowFilterBatch":
+        return RowFilterBatch([None if a < 0 else filters[a] for a in self.assign])
+
+    def slice(self, lo: int, hi: int) -> "RowFilterBatch":
+        """Every filter restricted to rows ``[lo, hi)`` (:meth:`RowFilter.slice`), same query assignment: what one rank of a
+        sharded index searches with."""
+        out = self._with([f.slice(lo, hi) for f in self.filters])
+        if not self.filters:
+            out.n = None
+        for f in out.filters:
+            f.generation = self.generation
+        out.generation = self.generation
+        return out
+
+    def to(self, device) -> "RowFilterBatch":
+        out = self._with([f.to(device) for f in self.filters])
+        if not self.filters:
+            out.query_filter = out.query_filter.to(_device(device))
+            out.bits = out.bits.to(_device(device))
+        return out
+
+    def __repr__(self) -> str:
+        return f"RowFilterBatch(B={len(self)}, F={len(self.filters)}, n={self.n}, device={self.bits.device})"
